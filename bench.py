@@ -1,6 +1,6 @@
 """bench.py -- meta-steps/sec of the `--copy-grad` meta-transfer step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or started plainly --
     without RANK / WORLD_SIZE in the environment the script starts its own N ranks under torch.distributed.run: `self_launch_command`)
 
@@ -11,12 +11,13 @@ accumulation, ONE all-reduce of the flat meta-gradient (N > 1), Adam, and the lo
 Workload (all N): 8 synthetic meta-tasks, k_train = k_valid = 8 utterances of 1000 frames x 161 bins, 100 labels,
 enc2/dec4 d512 h8 r100 V=3765, fp32, dropout 0 -- tasks sharded round-robin over the ranks (8/N per GPU, strong scaling;
 SURVEY.md 8(d)).  `value`: inputs resident in HBM when the timed region starts, nothing but the meta-steps
-inside it (no profiling events).  Reported next to it in the same line: the same steps with every batch uploaded from pinned
-host memory inside the timed span (`with_h2d`, what the reference's span contains), the README-faithful 3-task / 1-GPU
-configuration (BASELINE.json configs[1]), the dropout-0.1 variant, and -- after the timed region -- a SERIAL profiling step that
+inside it (no profiling events).  A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given (`dump_outputs`) and prints the line.  With --full it goes on, and reports in the same line: the same
+steps with every batch uploaded from pinned host memory inside the timed span (`with_h2d`, what the reference's span
+contains), the README-faithful 3-task / 1-GPU configuration (BASELINE.json configs[1]), the dropout-0.1 variant, and -- after the timed region -- a SERIAL profiling step that
 brackets EVERY library launch with HIP events on its own stream: the `roofline` object names the kernel class with the largest
 accumulated time over ALL classes (convolutions, GEMM engines, attention, LayerNorm, ...) and carries the per-class table.
-`cpu_baseline`: the CPU oracle on the host cores (bounded sample, N = 1 only).
+`cpu_baseline` (--full): the CPU oracle on the host cores (bounded sample, N = 1 only).
 """
 import argparse
 import contextlib
@@ -576,6 +577,28 @@ def h2_frac(trainer):
                 worst_operand=max(cen, key=lambda k_: cen[k_][0]), limit_lt16=trainer.h2_limit, sampled_every=trainer.h2_check_every)
 
 
+DUMP_SAMPLE = 1 << 22          # elements kept of a larger output (16 MB in float32): a fixed, seeded choice of positions
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller after the LAST timed step, one DIR/<name>.npy each -- `theta` (the
+    flat parameters after the outer step), `meta_grad` (the flat meta-gradient that step applied, summed over the ranks) and
+    `last_step` (float64: validation loss summed over the tasks, CER edits, characters).  Device tensors are written in float32;
+    one of more than DUMP_SAMPLE elements is cut to DUMP_SAMPLE of them at positions drawn once from a fixed seed (sorted, the same
+    positions in every run of the same size), so the files stay below 64 MB in all.  Inputs and initial parameters are seeded, so
+    two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            a = v.detach().float().reshape(-1).cpu().numpy()
+            if a.size > DUMP_SAMPLE:
+                a = a[np.sort(np.random.default_rng(12345).choice(a.size, DUMP_SAMPLE, replace=False))]
+        else:
+            a = np.asarray(v, dtype=np.float64).reshape(-1)
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a))
+
+
 def eval_leg(mtl, trainer, model, vocab, args, k, frames, labels, dev, reps=4, decode_steps=300):
     """SURVEY 8(f) f2, measured: (a) what the in-loop validation runs per batch (transient_trainer.py:280-331: eval mode, no autograd,
     `forward_one_batch` = teacher-forced pass + loss + CER strings) and (b) test-time greedy decoding (Transformer.evaluate ->
@@ -713,7 +736,24 @@ def main_lm(a, mtl_amd, mdist, dev, rank, world):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
-    # serial profiling iteration: every launch bracketed with events (same scheme as the ASR workload)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(theta=torch.cat([p_.detach().reshape(-1) for p_ in model.parameters()]),
+                                          last_step=[float(last[0])] + [float(v) for v in last[1]]))
+    out = None
+    if rank == 0:
+        out = dict(metric='meta-steps/sec', value=a.steps / dt, unit='meta-steps/s', n_gpus=world, steps=a.steps, warmup=a.warmup,
+                   ms_per_step=dt / a.steps * 1e3, higher_is_better=True, scaling='strong', vs_baseline=None, dtype='f32', data='synthetic',
+                   config=dict(workload='lm/main_meta_transfer.py meta loop (first-order reading, parity unpinned vs the reference loop): '
+                                        '2-layer LSTM d%d V%d, bptt %d, batch %d, %d synthetic corpora (%d per GPU), dropout %.1f'
+                                        % (c['nhid'], c['ntoken'], c['bptt'], c['batch_size'], n, len(mine), c['dropout']),
+                               tasks=n, parallelism='task-sharded dp%d' % world, collective=mdist.backend_name(), **{k: c[k] for k in ('bptt', 'batch_size', 'nhid', 'ntoken')}),
+                   last_step=dict(weighted_val_loss=last[0]))
+    if not a.full:
+        if rank == 0:
+            emit(out)
+        mdist.barrier()
+        return
+    # --full: serial profiling iteration: every launch bracketed with events (same scheme as the ASR workload)
     prof = LaunchProfiler(mtl_amd._lib.lib(), dev)
     eng = model.engine
     real = eng.lib
@@ -730,7 +770,6 @@ def main_lm(a, mtl_amd, mdist, dev, rank, world):
         cc['time'] += e0.elapsed_time(e1) * 1e-3
         cc['work'] += work or 0.0
         cc['launches'] += 1
-    out = None
     if rank == 0:
         passes = 2 * max(len(mine), 1)
         table = {}
@@ -743,17 +782,10 @@ def main_lm(a, mtl_amd, mdist, dev, rank, world):
             table[cls] = row
         dom = next(k for k in table if 'frac' in table[k])
         dr, dc = table[dom], classes[dom]
-        out = dict(metric='meta-steps/sec', value=a.steps / dt, unit='meta-steps/s', n_gpus=world, steps=a.steps, warmup=a.warmup,
-                   ms_per_step=dt / a.steps * 1e3, higher_is_better=True, scaling='strong', vs_baseline=None, dtype='f32', data='synthetic',
-                   config=dict(workload='lm/main_meta_transfer.py meta loop (first-order reading, parity unpinned vs the reference loop): '
-                                        '2-layer LSTM d%d V%d, bptt %d, batch %d, %d synthetic corpora (%d per GPU), dropout %.1f'
-                                        % (c['nhid'], c['ntoken'], c['bptt'], c['batch_size'], n, len(mine), c['dropout']),
-                               tasks=n, parallelism='task-sharded dp%d' % world, collective=mdist.backend_name(), **{k: c[k] for k in ('bptt', 'batch_size', 'nhid', 'ntoken')}),
-                   roofline=dict(bound=dr['bound'], kernel=dom, symbols=dr['symbols'], achieved=dr['achieved'], peak=dr['peak'], unit=dr['unit'],
-                                 frac=dr['frac'], traffic=None, work_per_launch=dc['work'] / dc['launches'],
-                                 avg_launch_ms=dc['time'] / dc['launches'] * 1e3, launches_timed=dc['launches'],
-                                 timing='HIP events around every library call of one serial meta-iteration', per_class=table),
-                   last_step=dict(weighted_val_loss=last[0]))
+        out['roofline'] = dict(bound=dr['bound'], kernel=dom, symbols=dr['symbols'], achieved=dr['achieved'], peak=dr['peak'], unit=dr['unit'],
+                               frac=dr['frac'], traffic=None, work_per_launch=dc['work'] / dc['launches'],
+                               avg_launch_ms=dc['time'] / dc['launches'] * 1e3, launches_timed=dc['launches'],
+                               timing='HIP events around every library call of one serial meta-iteration', per_class=table)
         if world == 1 and not a.no_cpu_baseline:
             from oracle import lm_refimpl as LR           # checker-side restatement: the cpu_baseline leg only
             threads = a.cpu_threads or min(32, physical_cores(), HOST.get("effective_cpus") or 32)
@@ -822,6 +854,89 @@ def power_limited_ceiling(dev, achieved, peak):
     return out
 
 
+def roofline_object(classes, n_launch, serial_wall, passes, conv_mode, dev):
+    """--full: the `roofline` object from the per-class launch timings of the serial profiling step (`serial_profile`): the kernel
+    family with the largest accumulated time, its achieved rate against the roof of its instructions, the per-family and per-class
+    tables, and the live power-limited ceiling of the probe library when that family is matrix-bound."""
+    pmc = {}
+    try:
+        pmc = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
+    except Exception:
+        pass
+    table = {}
+    for cls, c in sorted(classes.items(), key=lambda kv: -kv[1]['time']):
+        # "pass" = forward + backward of ONE task's batch (a task-batched pass of nt tasks counts nt)
+        row = dict(ms_per_pass=c['time'] / passes * 1e3, launches_per_pass=c['launches'] / passes, symbols=c['symbols'])
+        if c['unit'] is not None and c['work'] > 0:
+            peak, unit, bound = peak_of(cls, c['unit'], conv_mode)
+            ach = c['work'] / c['time'] / (1e12 if c['unit'] == 'flop' else 1e9)
+            row.update(bound=bound, achieved=ach, peak=peak, unit=unit, frac=ach / peak)
+            if 'wgrad_sp' in c['symbols']:
+                # `achieved` counts the ALGORITHMIC (dense-equivalent) FLOPs of the reference op; the kernel issues half of them as
+                # 2:4-sparse instructions, whose peak is twice the dense one
+                row.update(frac_of_sparse_peak=ach / (2 * peak), note='frac: dense-equivalent FLOPs / dense two-piece-fp16 peak (838.9 TF); '
+                           'frac_of_sparse_peak: the same FLOPs / the 2:4-sparse peak (1677.7 TF) the instructions issue at')
+        table[cls] = row
+    for cls, row in table.items():
+        if cls in pmc:
+            row['traffic'] = pmc[cls]             # HBM bytes per launch (separate --pmc FETCH_SIZE / WRITE_SIZE passes, profiles/)
+            ab = classes[cls].get('abytes', 0.0) / max(classes[cls]['launches'], 1)
+            if ab > 0:
+                row['algorithmic_bytes'] = ab
+                row['traffic_over_algorithmic'] = pmc[cls] / ab
+    # ---- aggregate by rocprofv3 symbol family; the dominant family (largest accumulated time) is the `roofline` object
+    fams = {}
+    for cls, c in classes.items():
+        if c['unit'] is None or c['work'] <= 0:
+            continue
+        f = fams.setdefault(family_of(cls, c['symbols']), dict(time=0.0, work=0.0, launches=0, classes=[], unit=c['unit'], traffic=0.0,
+                                                               traffic_known=True, abytes=0.0))
+        f['abytes'] += c.get('abytes', 0.0)
+        f['time'] += c['time']
+        f['work'] += c['work']
+        f['launches'] += c['launches']
+        f['classes'].append(cls)
+        if cls in pmc:
+            f['traffic'] += pmc[cls] * c['launches']
+        else:
+            f['traffic_known'] = False
+    fam_table = {}
+    for name, f in sorted(fams.items(), key=lambda kv: -kv[1]['time']):
+        peak, unit, bound = peak_of(f['classes'][0], f['unit'], conv_mode)
+        ach = f['work'] / f['time'] / (1e12 if f['unit'] == 'flop' else 1e9)
+        fam_table[name] = dict(ms_per_pass=f['time'] / passes * 1e3, launches_per_pass=f['launches'] / passes, bound=bound, achieved=ach,
+                               peak=peak, unit=unit, frac=ach / peak, classes=f['classes'],
+                               traffic=(f['traffic'] / f['launches']) if (f['traffic_known'] and f['launches']) else None)
+        if name == 'conv3x3_wgrad_sp_kernel':
+            fam_table[name]['frac_of_sparse_peak'] = ach / (2 * peak)
+    dom = next(iter(fam_table))                      # (sorted by accumulated time)
+    df, dr = fams[dom], fam_table[dom]
+    arith = ('split-bf16 x3: 6 v_mfma_f32_32x32x16_bf16 per fp32-equivalent step, peak = dense bf16 / 6' if dr['peak'] == PEAK_X3_TFLOPS else (
+        'two fp16 pieces (h2): 3 v_mfma_f32_32x32x16_f16 per fp32-equivalent step, peak = dense fp16 / 3' if dr['peak'] == PEAK_H2_TFLOPS else (
+            'exact fp32 MFMA' if dr['bound'] == 'mfma' else 'HBM streaming')))
+    roofline = dict(bound=dr['bound'], kernel=dom, symbols=dom, achieved=dr['achieved'], peak=dr['peak'], unit=dr['unit'],
+                    frac=dr['frac'], traffic=dr['traffic'], algorithmic_bytes=df['abytes'] / max(df['launches'], 1),
+                    work_per_launch=df['work'] / df['launches'], avg_launch_ms=df['time'] / df['launches'] * 1e3,
+                    launches_timed=df['launches'], ms_per_pass=dr['ms_per_pass'], classes=dr['classes'],
+                    selection='rocprofv3 symbol family with the largest accumulated time over ALL library launches of a serial meta-step '
+                              '(per-layer / per-shape classes of one kernel template are summed: `per_family`; the split by layer and '
+                              'direction stays in `per_class`)',
+                    timing='HIP events on the launch stream around every library call, serial step after the timed region '
+                           '(task lanes, side stream and command-list replay off)',
+                    traffic_source='(2 x FETCH_SIZE + WRITE_SIZE) x 1024 bytes per launch, launch-weighted over the family; separate rocprofv3 '
+                                   '--pmc passes (profiles/pmc_traffic.json)',
+                    arithmetic=arith,
+                    serial_step=dict(launches_per_pass=n_launch / passes, gpu_ms_per_pass=sum(c['time'] for c in classes.values()) / passes * 1e3,
+                                     gpu_span_ms_per_pass=serial_wall / passes * 1e3),
+                    per_family=fam_table, per_class=table)
+    if dr['bound'] == 'mfma':
+        try:
+            roofline['power_limited'] = power_limited_ceiling(dev, dr['achieved'], dr['peak'])
+        except Exception as e:                       # a measurement aid must never cost the bench line
+            roofline['power_limited'] = dict(error=repr(e))
+    return roofline
+
+
 def physical_cores():
     try:
         import psutil
@@ -853,9 +968,13 @@ def main():
     ap.add_argument('--k', type=int, default=8)
     ap.add_argument('--frames', type=int, default=1000)
     ap.add_argument('--labels', type=int, default=100)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='after the headline: the serial roofline step, the extra legs and the CPU baseline '
+                    '(a plain run measures the headline steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy '
+                    '(see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--cpu-threads', type=int, default=0)
-    ap.add_argument('--no-extras', action='store_true', help='only the headline timed region + the serial roofline step')
+    ap.add_argument('--no-extras', action='store_true', help='--full without the extra legs: the headline timed region + the serial roofline step')
     ap.add_argument('--dropout', type=float, default=0.0, help='diagnostics: run the headline region and the serial profile with this dropout rate (the extras always report 0.1)')
     ap.add_argument('--lanes', action='store_true', help='per-task pass chains on concurrent lanes instead of task-batched passes (MTL_BATCH_TASKS=0)')
     ap.add_argument('--serial', action='store_true', help='no task lanes / side stream / replay (for rocprofv3 per-kernel durations)')
@@ -945,6 +1064,8 @@ def main():
     # ---- the headline number: K meta-steps, inputs resident, nothing else inside the timed region
     dt, last = timed_steps(trainer, model, vocab, tasks, my_tasks, a.tasks, inner, outer, args, a.steps, a.warmup, mdist, dev)
     host_stats = {k: round(v, 2) for k, v in HOST_ENQUEUE.items()}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(theta=model.flat_parameters, meta_grad=model._G, last_step=last))
 
     # (bit-level fingerprint of theta after the timed steps: tests compare schedules / collectives that must not change a single bit)
     th = model.flat_parameters
@@ -964,88 +1085,12 @@ def main():
                  tasks_per_rank=[len(mdist.shard_tasks(a.tasks, r, world)) for r in range(world)],
                  per_rank_ms_per_step=PER_RANK.get('ms_per_step') or [round(dt / a.steps * 1e3, 3)], replicas_bit_identical=bool(lo == hi),
                  launcher=os.environ.get('MTL_BENCH_LAUNCHER', 'external' if 'RANK' in os.environ else 'none'))
-    # ---- serial profiling step (every rank runs it: it contains the collective; only rank 0 reports)
-    classes, n_launch, serial_wall = serial_profile(mtl_amd, trainer, model, vocab, tasks, my_tasks, a.tasks, inner, outer, args, dev)
+    # ---- --full: serial profiling step (every rank runs it: it contains the collective; only rank 0 reports)
+    if a.full:
+        classes, n_launch, serial_wall = serial_profile(mtl_amd, trainer, model, vocab, tasks, my_tasks, a.tasks, inner, outer, args, dev)
     out = None
     if rank == 0:
-        eng = model.engine
         passes = 2 * max(len(my_tasks), 1)
-        pmc = {}
-        try:
-            pmc = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
-        except Exception:
-            pass
-        table = {}
-        for cls, c in sorted(classes.items(), key=lambda kv: -kv[1]['time']):
-            # "pass" = forward + backward of ONE task's batch (a task-batched pass of nt tasks counts nt)
-            row = dict(ms_per_pass=c['time'] / passes * 1e3, launches_per_pass=c['launches'] / passes, symbols=c['symbols'])
-            if c['unit'] is not None and c['work'] > 0:
-                peak, unit, bound = peak_of(cls, c['unit'], eng.conv_mode)
-                ach = c['work'] / c['time'] / (1e12 if c['unit'] == 'flop' else 1e9)
-                row.update(bound=bound, achieved=ach, peak=peak, unit=unit, frac=ach / peak)
-                if 'wgrad_sp' in c['symbols']:
-                    # `achieved` counts the ALGORITHMIC (dense-equivalent) FLOPs of the reference op; the kernel issues half of them as
-                    # 2:4-sparse instructions, whose peak is twice the dense one
-                    row.update(frac_of_sparse_peak=ach / (2 * peak), note='frac: dense-equivalent FLOPs / dense two-piece-fp16 peak (838.9 TF); '
-                               'frac_of_sparse_peak: the same FLOPs / the 2:4-sparse peak (1677.7 TF) the instructions issue at')
-            table[cls] = row
-        for cls, row in table.items():
-            if cls in pmc:
-                row['traffic'] = pmc[cls]             # HBM bytes per launch (separate --pmc FETCH_SIZE / WRITE_SIZE passes, profiles/)
-                ab = classes[cls].get('abytes', 0.0) / max(classes[cls]['launches'], 1)
-                if ab > 0:
-                    row['algorithmic_bytes'] = ab
-                    row['traffic_over_algorithmic'] = pmc[cls] / ab
-        # ---- aggregate by rocprofv3 symbol family; the dominant family (largest accumulated time) is the `roofline` object
-        fams = {}
-        for cls, c in classes.items():
-            if c['unit'] is None or c['work'] <= 0:
-                continue
-            f = fams.setdefault(family_of(cls, c['symbols']), dict(time=0.0, work=0.0, launches=0, classes=[], unit=c['unit'], traffic=0.0,
-                                                                   traffic_known=True, abytes=0.0))
-            f['abytes'] += c.get('abytes', 0.0)
-            f['time'] += c['time']
-            f['work'] += c['work']
-            f['launches'] += c['launches']
-            f['classes'].append(cls)
-            if cls in pmc:
-                f['traffic'] += pmc[cls] * c['launches']
-            else:
-                f['traffic_known'] = False
-        fam_table = {}
-        for name, f in sorted(fams.items(), key=lambda kv: -kv[1]['time']):
-            peak, unit, bound = peak_of(f['classes'][0], f['unit'], eng.conv_mode)
-            ach = f['work'] / f['time'] / (1e12 if f['unit'] == 'flop' else 1e9)
-            fam_table[name] = dict(ms_per_pass=f['time'] / passes * 1e3, launches_per_pass=f['launches'] / passes, bound=bound, achieved=ach,
-                                   peak=peak, unit=unit, frac=ach / peak, classes=f['classes'],
-                                   traffic=(f['traffic'] / f['launches']) if (f['traffic_known'] and f['launches']) else None)
-            if name == 'conv3x3_wgrad_sp_kernel':
-                fam_table[name]['frac_of_sparse_peak'] = ach / (2 * peak)
-        dom = next(iter(fam_table))                      # (sorted by accumulated time)
-        df, dr = fams[dom], fam_table[dom]
-        arith = ('split-bf16 x3: 6 v_mfma_f32_32x32x16_bf16 per fp32-equivalent step, peak = dense bf16 / 6' if dr['peak'] == PEAK_X3_TFLOPS else (
-            'two fp16 pieces (h2): 3 v_mfma_f32_32x32x16_f16 per fp32-equivalent step, peak = dense fp16 / 3' if dr['peak'] == PEAK_H2_TFLOPS else (
-                'exact fp32 MFMA' if dr['bound'] == 'mfma' else 'HBM streaming')))
-        roofline = dict(bound=dr['bound'], kernel=dom, symbols=dom, achieved=dr['achieved'], peak=dr['peak'], unit=dr['unit'],
-                        frac=dr['frac'], traffic=dr['traffic'], algorithmic_bytes=df['abytes'] / max(df['launches'], 1),
-                        work_per_launch=df['work'] / df['launches'], avg_launch_ms=df['time'] / df['launches'] * 1e3,
-                        launches_timed=df['launches'], ms_per_pass=dr['ms_per_pass'], classes=dr['classes'],
-                        selection='rocprofv3 symbol family with the largest accumulated time over ALL library launches of a serial meta-step '
-                                  '(per-layer / per-shape classes of one kernel template are summed: `per_family`; the split by layer and '
-                                  'direction stays in `per_class`)',
-                        timing='HIP events on the launch stream around every library call, serial step after the timed region '
-                               '(task lanes, side stream and command-list replay off)',
-                        traffic_source='(2 x FETCH_SIZE + WRITE_SIZE) x 1024 bytes per launch, launch-weighted over the family; separate rocprofv3 '
-                                       '--pmc passes (profiles/pmc_traffic.json)',
-                        arithmetic=arith,
-                        serial_step=dict(launches_per_pass=n_launch / passes, gpu_ms_per_pass=sum(c['time'] for c in classes.values()) / passes * 1e3,
-                                         gpu_span_ms_per_pass=serial_wall / passes * 1e3),
-                        per_family=fam_table, per_class=table)
-        if dr['bound'] == 'mfma':
-            try:
-                roofline['power_limited'] = power_limited_ceiling(dev, dr['achieved'], dr['peak'])
-            except Exception as e:                       # a measurement aid must never cost the bench line
-                roofline['power_limited'] = dict(error=repr(e))
         ms = dt / a.steps * 1e3
         out = dict(metric='meta-steps/sec', value=a.steps / dt, unit='meta-steps/s', n_gpus=world, steps=a.steps, warmup=a.warmup,
                    ms_per_step=ms, higher_is_better=True, scaling='strong', vs_baseline=None, dtype=DTYPE[model.engine.conv_mode],
@@ -1068,9 +1113,11 @@ def main():
                                                 'x3': '3x3 convolutions as exact 3-way bf16 splits of fp32 operands, fp32 accumulate '
                                                       '(fp32-class error, same test tolerances as the fp32-MFMA kernels)',
                                                 'f32': 'fp32 MFMA'}[model.engine.conv_mode]),
-                   h2_subnormal_frac=h2_frac(trainer), roofline=roofline, host_enqueue_ms=host_stats, host=dict(HOST), multi_gpu=multi, last_step=dict(val_loss=last[0] / a.tasks, cer_edits=last[1], chars=last[2]), theta_checksum=theta_ck)
+                   h2_subnormal_frac=h2_frac(trainer), host_enqueue_ms=host_stats, host=dict(HOST), multi_gpu=multi, last_step=dict(val_loss=last[0] / a.tasks, cer_edits=last[1], chars=last[2]), theta_checksum=theta_ck)
+        if a.full:
+            out['roofline'] = roofline_object(classes, n_launch, serial_wall, passes, model.engine.conv_mode, dev)
 
-    extras = world == 1 and not a.no_extras
+    extras = a.full and world == 1 and not a.no_extras
 
     def run_extras():
         k3 = max(a.steps // 2, 3)
@@ -1172,7 +1219,7 @@ def main():
             import traceback
             out['extras_error'] = repr(e)
             print('bench extras failed:\n' + traceback.format_exc(), file=sys.stderr, flush=True)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         # torch's CPU kernels do not scale to every core of a large host (measured on the 128-core GPU node: 11.1 s per task at
         # 128 threads, 3.9 s at 32, 4.2 s at 8), so the baseline is timed at the physical core count, at 32 and at 8 threads
         # (SURVEY's 8-core figure) and the FASTEST is reported as `value`, with its thread count in `cores`

@@ -6,6 +6,7 @@ synthetic batches and stores inputs + expected outputs as data fixtures.  Recipe
 
     python oracle/make_golden.py            # F0 (tiny), F1 (small-real), J0 (joint), B0 (beam search), G0 (greedy search)
     python oracle/make_golden.py --ns       # additionally the north-star-size checksum record (~1 min)
+    python oracle/make_golden.py --only C0  # the checkpoint written by the reference's save_meta_model (tests/golden/C0.th.gz)
 """
 import argparse
 import hashlib
@@ -447,6 +448,50 @@ def run_frontend_fixture():
     print('S0 written: spectrogram', store['spect_norm'].shape)
 
 
+def run_checkpoint_fixture():
+    """C0.th.gz: the checkpoint format, both directions.  A `.th` written by this package (tests/golden_util.py
+    meta_checkpoint_of_this_package) goes through the reference's own load path (its Vocab class, init_transformer_model,
+    load_state_dict, optimizer state), takes one more Adam step there and is written by the reference's save_meta_model; that file is
+    the fixture, gzip-compressed.  The reference runs in a subprocess (its `utils` package must not meet this process's modules)."""
+    import shutil
+    import subprocess
+    import tempfile
+    sys.path.insert(0, ROOT)
+    from tests import golden_util as gu
+    tmp = tempfile.mkdtemp()
+    ours = gu.meta_checkpoint_of_this_package(tmp)
+    script = r"""
+import sys, torch
+sys.path.insert(0, %r)
+from oracle.make_golden import bootstrap_reference
+bootstrap_reference()
+from utils.data import Vocab
+from utils import functions as RF
+ck = torch.load(%r, map_location='cpu', weights_only=False)
+assert type(ck['vocab']).__module__ == 'utils.data' and type(ck['vocab']) is Vocab
+a = ck['args']
+model = RF.init_transformer_model(a, ck['vocab'], train=True, is_factorized=a.is_factorized, r=a.r)
+model.load_state_dict(ck['model_state_dict'])
+io = torch.optim.SGD(model.parameters(), lr=a.lr); oo = torch.optim.Adam(model.parameters(), lr=a.meta_lr)
+io.load_state_dict(ck['inner_opt'].state_dict()); oo.load_state_dict(ck['outer_opt'].state_dict())
+assert len(oo.state) == len(list(model.parameters())) and ck['epoch'] == 3
+for p in model.parameters():
+    p.grad = torch.full_like(p, -0.02)
+oo.step()
+a.save_folder, a.name = 'save', 'theirs'       # (relative to the working directory: a fixed string in the pickled args)
+RF.save_meta_model(model, ck['vocab'], 4, io, oo, {'avg_valid_cer': 1.5}, a)
+print('REFERENCE_OK')
+""" % (ROOT, ours)
+    out = subprocess.run([sys.executable, '-c', script], capture_output=True, text=True, cwd=tmp, timeout=600,
+                         env=dict(os.environ, PYTHONPATH='/root/reference'))
+    assert 'REFERENCE_OK' in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+    import gzip
+    with open(os.path.join(tmp, 'save', 'theirs', 'epoch_4.th'), 'rb') as f, open(os.path.join(OUT, 'C0.th.gz'), 'wb') as g:
+        with gzip.GzipFile(filename='', mode='wb', fileobj=g, mtime=0, compresslevel=9) as z:
+            z.write(f.read())
+    shutil.rmtree(tmp)
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--ns', action='store_true')
@@ -458,6 +503,9 @@ if __name__ == '__main__':
     if a.only == 'S0':
         sys.path.insert(0, ROOT)
         run_frontend_fixture()
+        raise SystemExit(0)
+    if a.only == 'C0':
+        run_checkpoint_fixture()
         raise SystemExit(0)
     torch = bootstrap_reference()
     todo = [a.only] if a.only else (['F0', 'F1', 'J0', 'B0', 'G0'] + (['NS'] if a.ns else []) + ['L0'])

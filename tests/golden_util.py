@@ -93,3 +93,46 @@ def label_words(id2label, specials):
             st = st.replace(tok, '')
         return len(st.replace('  ', ' ').split())
     return num_words
+
+
+def meta_checkpoint_of_this_package(folder):
+    """The `.th` of tests/test_host.py's checkpoint cross-load (and of oracle/make_golden.py --only C0, which hands it to the reference):
+    save_meta_model of a small non-factorized model (the VGG front-end at its fixed width, one encoder and one decoder layer of width
+    16) after one Adam step, so optimizer state exists -> its path.  The weights are set to period-8 patterns of exact values first:
+    what is checked is the file's format, and the reference's copy of the file (tests/golden/C0.th.gz) then compresses to a few KB."""
+    import argparse
+    import mtl_amd
+    cfg = dict(num_enc_layers=1, num_dec_layers=1, num_heads=2, dim_model=16, dim_key=8, dim_value=8, dim_inner=16, dim_emb=16,
+               src_max_len=100, tgt_max_len=50)
+    args = dict(feat_extractor='vgg_cnn', sample_rate=16000, window_size=.02, feat='spectrogram', dim_input=161, dropout=0.0,
+                emb_trg_sharing=False, label_smoothing=0.0, name='ours', lr=1e-2, meta_lr=1e-3, k_train=2, k_valid=2, clip=False,
+                max_norm=400, save_every=1, save_folder=str(folder), cuda=False, is_factorized=False, r=100)
+    args.update({k: v for k, v in cfg.items() if k not in ('vocab_size', 'r')})
+    args = argparse.Namespace(**args)
+    vocab = mtl_amd.synthetic_vocab(64)
+    m = mtl_amd.init_transformer_model(args, vocab, is_factorized=False, r=100)
+    with torch.no_grad():
+        for i, p in enumerate(m.parameters()):                 # (phase and offset i / 1024 differ per tensor: no two of one shape are equal)
+            p.copy_((((torch.arange(p.numel()) + 3 * i) % 8).float() - 3.5).view_as(p) / 64 + i / 1024)
+    outer = torch.optim.Adam(m.parameters(), lr=args.meta_lr)
+    for i, p in enumerate(m.parameters()):
+        p.grad = torch.full_like(p, (i + 1) / 128)              # (per tensor too: the Adam moments differ from tensor to tensor)
+    outer.step()
+    return mtl_amd.save_meta_model(m, vocab, 3, torch.optim.SGD(m.parameters(), lr=args.lr), outer, {'avg_valid_cer': 2.0}, args)
+
+
+def pickle_globals(path):
+    """{(module, name)} a torch.save zip file's pickle refers to: what an unpickler must be able to import to load it"""
+    import pickletools
+    import zipfile
+    with zipfile.ZipFile(path) as zf:
+        pkl = zf.read([n for n in zf.namelist() if n.endswith('data.pkl')][0])
+    out, strings = set(), []
+    for op, arg, _ in pickletools.genops(pkl):
+        if op.name == 'GLOBAL':
+            out.add(tuple(arg.split(' ', 1)))
+        elif op.name == 'STACK_GLOBAL':
+            out.add(tuple(strings[-2:]))
+        if isinstance(arg, str):
+            strings.append(arg)
+    return out

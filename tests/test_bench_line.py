@@ -157,3 +157,24 @@ def test_bench_helpers_are_called_with_their_current_signatures():
             assert required <= n <= want[node.func.id], (node.func.id, node.lineno, n)
             seen[node.func.id] += 1
     assert all(v > 0 for v in seen.values()), seen
+
+
+def test_dump_outputs_are_float_arrays_of_a_fixed_sample(tmp_path):
+    """--dump-outputs DIR: one DIR/<name>.npy per output, float32 for device tensors and float64 for the read-back scalars; an output
+    larger than DUMP_SAMPLE elements is cut to DUMP_SAMPLE of them at the same sorted positions in every run, so two builds compare
+    element for element and the files stay below 64 MB in all"""
+    import numpy as np
+    import torch
+    bench = load_bench()
+    n = bench.DUMP_SAMPLE * 3 + 7
+    theta = torch.arange(n, dtype=torch.float32)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), dict(theta=theta, meta_grad=-theta, small=theta[:10], last_step=[12.5, 3, 40]))
+    got = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert sorted(got) == ['last_step', 'meta_grad', 'small', 'theta']
+    assert got['theta'].dtype == got['meta_grad'].dtype == got['small'].dtype == np.float32 and got['last_step'].dtype == np.float64
+    assert got['last_step'].tolist() == [12.5, 3.0, 40.0] and got['small'].tolist() == list(range(10))
+    idx = got['theta'].astype(np.int64)                   # theta[i] == i: the values are the sampled positions
+    assert idx.size == bench.DUMP_SAMPLE and (np.diff(idx) > 0).all() and idx[-1] < n and (got['meta_grad'] == -got['theta']).all()
+    assert all(np.array_equal(np.load(str(tmp_path / 'b' / (f + '.npy'))), v) for f, v in got.items())
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (f + '.npy'))) for f in got) < 64 << 20

@@ -223,7 +223,7 @@ def test_collective_sequence_is_rank_invariant_with_uneven_shards():
         assert ret[(rank, '1')] < 1e-6 and ret[(rank, '0')] < 1e-6 and ret[(rank, 'idle')], dict(ret)
 
 
-def _world4_worker(rank, world, port, ret):
+def _sharded_worker(rank, world, port, ret):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
     import types
@@ -239,7 +239,7 @@ def _world4_worker(rank, world, port, ret):
     params = list(model.parameters())
     adam = R.AdamState(params, 1e-3)
     mine = mdist.shard_tasks(n_tasks, rank, world)
-    assert len(mine) == 2
+    assert mine == list(range(rank, n_tasks, world)) and len(mine) == n_tasks // world
     trainer = mtl_amd.TransientTrainer()
     worst, same = 0.0, True
 
@@ -281,6 +281,17 @@ def test_world4_two_tasks_per_rank_three_iterations():
     replicated Adam steps every rank holds the same parameter BITS."""
     mgr = mp.Manager()
     ret = mgr.dict()
-    mp.spawn(_world4_worker, args=(4, 29623, ret), nprocs=4, join=True)
+    mp.spawn(_sharded_worker, args=(4, 29623, ret), nprocs=4, join=True)
     assert ret[0][0] < 1e-6, ret[0]
     assert all(ret[r][1] for r in range(4)), dict(ret)
+
+
+def test_world8_one_task_per_rank_three_iterations():
+    """BASELINE.json configs[2] exactly: 8 tasks on 8 ranks, ONE task per rank, over gloo on CPU (no device is opened, so all eight
+    ranks run at once whatever a shared GPU allows): the 8-way sliced all-reduce of the local parts equals the sequential
+    accumulation over m = 0..7 within 1e-6, and after each of three replicated Adam steps every rank holds the same parameter BITS."""
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_sharded_worker, args=(8, 29625, ret), nprocs=8, join=True)
+    assert ret[0][0] < 1e-6, ret[0]
+    assert all(ret[r][1] for r in range(8)), dict(ret)

@@ -249,64 +249,42 @@ def test_frontend_oracle_reproduces_its_committed_fixture():
         assert np.abs(got - z[key]).max() <= 2e-6 * np.abs(z[key]).max()
 
 
-REF = '/root/reference'
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason='needs the reference checkout (build container only)')
 def test_checkpoints_cross_load_with_the_real_reference(tmp_path):
-    """SURVEY 8(f) f4, both directions, in a subprocess that imports the REAL reference: (1) a `.th` written by the reference's
-    save_meta_model (after one Adam step, so optimizer state exists) loads here with identical weights, vocabulary and Adam
-    moments; (2) a `.th` written here is consumed by the reference's own load path (its classes, its load_state_dict)."""
-    import subprocess
-    import sys
+    """SURVEY 8(f) f4, both directions, against tests/golden/C0.th.gz (oracle/make_golden.py --only C0): the REAL reference loaded the
+    `.th` this package writes (golden_util.meta_checkpoint_of_this_package) through its own load path -- its Vocab class,
+    init_transformer_model, load_state_dict of the weights and of both optimizers -- took one more Adam step and wrote C0.th with its
+    save_meta_model.  (1) That file loads here with identical weights, vocabulary and Adam moments; (2) the file written here has the
+    layout of the reference's: the same entries, parameter names, shapes and dtypes, optimizer classes and state, and its pickle refers
+    to nothing the reference's own file does not (so the reference's unpickler and strict load_state_dict accept it)."""
     import mtl_amd
-    z, cfg, spec = gu.load('F0')
-    args = make_args(cfg, save_folder=str(tmp_path), name='ours')
-    args.is_factorized, args.r, args.cuda = False, 100, False
-    vocab = mtl_amd.synthetic_vocab(64)
-    m = mtl_amd.init_transformer_model(args, vocab, is_factorized=False, r=100)
-    outer = torch.optim.Adam(m.parameters(), lr=args.meta_lr)
-    for p in m.parameters():
-        p.grad = torch.full_like(p, 0.01)
-    outer.step()
-    ours = mtl_amd.save_meta_model(m, vocab, 3, torch.optim.SGD(m.parameters(), lr=args.lr), outer, {'avg_valid_cer': 2.0}, args)
-    script = r"""
-import sys, torch
-sys.path.insert(0, %r)
-from oracle.make_golden import bootstrap_reference
-bootstrap_reference()
-import argparse
-from utils.data import Vocab
-from utils import functions as RF
-# (2) our file through the reference's load path (its torch.load call predates weights_only, so the dict is read explicitly)
-ck = torch.load(%r, map_location='cpu', weights_only=False)
-assert type(ck['vocab']).__module__ == 'utils.data' and type(ck['vocab']) is Vocab
-a = ck['args']
-model = RF.init_transformer_model(a, ck['vocab'], train=True, is_factorized=a.is_factorized, r=a.r)
-model.load_state_dict(ck['model_state_dict'])
-io = torch.optim.SGD(model.parameters(), lr=a.lr); oo = torch.optim.Adam(model.parameters(), lr=a.meta_lr)
-io.load_state_dict(ck['inner_opt'].state_dict()); oo.load_state_dict(ck['outer_opt'].state_dict())
-assert len(oo.state) == len(list(model.parameters())) and ck['epoch'] == 3
-# (1) a checkpoint written by the reference itself
-for p in model.parameters():
-    p.grad = torch.full_like(p, -0.02)
-oo.step()
-a.save_folder, a.name = %r, 'theirs'
-RF.save_meta_model(model, ck['vocab'], 4, io, oo, {'avg_valid_cer': 1.5}, a)
-print('REFERENCE_OK')
-""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), ours, str(tmp_path))
-    env = dict(os.environ, PYTHONPATH=REF)
-    out = subprocess.run([sys.executable, '-c', script], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
-    assert 'REFERENCE_OK' in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
-    theirs = os.path.join(str(tmp_path), 'theirs', 'epoch_4.th')
+    import gzip
+    theirs = str(tmp_path / 'C0.th')
+    with gzip.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'C0.th.gz'), 'rb') as f, open(theirs, 'wb') as g:
+        g.write(f.read())
     m2, v2, i2, o2, ep, met, a2 = mtl_amd.load_meta_model(theirs)
-    assert ep == 4 and met['avg_valid_cer'] == 1.5 and type(v2) is mtl_amd.Vocab and v2.id2label == vocab.id2label
+    assert ep == 4 and met['avg_valid_cer'] == 1.5 and type(v2) is mtl_amd.Vocab and v2.id2label == mtl_amd.synthetic_vocab(64).id2label
     raw = mtl_amd.functions.load_checkpoint_dict(theirs)
     for (n, p) in m2.named_parameters():
         assert torch.equal(p, raw['model_state_dict'][n])
-    st = o2.state_dict()['state']
+    st, st_raw = o2.state_dict()['state'], raw['outer_opt'].state_dict()['state']
     assert len(st) == len(list(m2.parameters())) and float(st[0]['step']) == 2.0
-    assert torch.equal(st[0]['exp_avg'], raw['outer_opt'].state_dict()['state'][0]['exp_avg'])
+    assert all(torch.equal(st[i][k], st_raw[i][k]) for i in st for k in ('exp_avg', 'exp_avg_sq'))
+    # (2) this package's file against the reference's
+    ours = gu.meta_checkpoint_of_this_package(tmp_path)
+    mine = mtl_amd.functions.load_checkpoint_dict(ours)
+    assert sorted(mine) == sorted(raw) and mine['epoch'] == 3
+    assert [(k, tuple(v.shape), v.dtype) for k, v in mine['model_state_dict'].items()] == \
+        [(k, tuple(v.shape), v.dtype) for k, v in raw['model_state_dict'].items()]
+    for k in ('inner_opt', 'outer_opt'):
+        assert type(mine[k]) is type(raw[k])
+        a_, b_ = mine[k].state_dict(), raw[k].state_dict()
+        assert [sorted(g) for g in a_['param_groups']] == [sorted(g) for g in b_['param_groups']]
+        assert [g['params'] for g in a_['param_groups']] == [g['params'] for g in b_['param_groups']]
+        assert sorted(a_['state']) == sorted(b_['state']) and all(sorted(a_['state'][i]) == sorted(b_['state'][i]) for i in a_['state'])
+    assert sorted(vars(mine['args'])) == sorted(vars(raw['args']))
+    assert mine['vocab'].id2label == raw['vocab'].id2label and type(mine['vocab']) is type(raw['vocab'])
+    g_ours, g_theirs = gu.pickle_globals(ours), gu.pickle_globals(theirs)
+    assert ('utils.data', 'Vocab') in g_ours and g_ours <= g_theirs, g_ours - g_theirs
 
 
 def test_spectrogram_dataset_constructed_as_the_reference_entry_script_does(tmp_path, capsys):

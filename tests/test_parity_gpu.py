@@ -471,9 +471,10 @@ def test_long_utterance_stress_config():
     assert out['hyp'].shape == (8, 101) and int(out['hyp'].max()) < cfg['vocab_size']
 
 
-def test_two_ranks_sharded_bench_equals_single_rank():
+def test_two_ranks_sharded_bench_equals_single_rank(tmp_path):
     """bench.py under torchrun with 2 ranks (sharing this box's single GPU over gloo): the sharded meta-step with ONE
-    all-reduce of G must reproduce the single-rank step (same loss / CER of the last step)."""
+    all-reduce of G must reproduce the single-rank step (same loss / CER of the last step), and so must what `--dump-outputs`
+    writes of that step (theta, the meta-gradient, the last step's loss / CER read-back)."""
     import json
     import os
     import subprocess
@@ -481,18 +482,31 @@ def test_two_ranks_sharded_bench_equals_single_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ['--steps', '2', '--warmup', '1', '--tasks', '4', '--k', '2', '--frames', '200', '--labels', '20', '--no-cpu-baseline']
     env = dict(os.environ, MTL_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1'] + common, capture_output=True, text=True,
-                         env=env, timeout=240)
+    one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--dump-outputs', str(tmp_path / 'one')] + common,
+                         capture_output=True, text=True, env=env, timeout=240)
     assert one.returncode == 0, one.stderr[-2000:]
     two = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-                          '127.0.0.1', '--master-port', '29733', os.path.join(root, 'bench.py'), '--gpus', '2'] + common,
-                         capture_output=True, text=True, env=env, timeout=240)
+                          '127.0.0.1', '--master-port', '29733', os.path.join(root, 'bench.py'), '--gpus', '2',
+                          '--dump-outputs', str(tmp_path / 'two')] + common, capture_output=True, text=True, env=env, timeout=240)
     assert two.returncode == 0, two.stderr[-2000:]
     j1 = json.loads([l for l in one.stdout.splitlines() if l.startswith('{')][-1])
     j2 = json.loads([l for l in two.stdout.splitlines() if l.startswith('{')][-1])
     assert j2['n_gpus'] == 2 and j1['n_gpus'] == 1 and j2['scaling'] == 'strong'
     assert j1['last_step']['chars'] == j2['last_step']['chars'] and j1['last_step']['cer_edits'] == j2['last_step']['cer_edits']
     assert abs(j1['last_step']['val_loss'] - j2['last_step']['val_loss']) < 1e-4 * abs(j1['last_step']['val_loss'])
+    # the dumped outputs: the line's read-back, and theta / meta-gradient of the single-rank and the sharded run
+    d = {w: {n: np.load(str(tmp_path / w / (n + '.npy'))) for n in ('theta', 'meta_grad', 'last_step')} for w in ('one', 'two')}
+    for w, j in (('one', j1), ('two', j2)):
+        assert d[w]['theta'].dtype == np.float32 and d[w]['meta_grad'].dtype == np.float32 and d[w]['last_step'].dtype == np.float64
+        assert d[w]['theta'].size == d[w]['meta_grad'].size and np.isfinite(d[w]['meta_grad']).all() and float(np.abs(d[w]['meta_grad']).max()) > 0
+        assert abs(d[w]['last_step'][0] / 4 - j['last_step']['val_loss']) <= 1e-6 * abs(j['last_step']['val_loss'])
+        assert d[w]['last_step'][1:].tolist() == [j['last_step']['cer_edits'], j['last_step']['chars']]
+    a64 = {w: {n: d[w][n].astype(np.float64) for n in ('theta', 'meta_grad')} for w in d}
+    rel = float(np.linalg.norm(a64['two']['theta'] - a64['one']['theta']) / np.linalg.norm(a64['one']['theta']))
+    cos = float(a64['two']['meta_grad'] @ a64['one']['meta_grad'] / np.linalg.norm(a64['two']['meta_grad']) / np.linalg.norm(a64['one']['meta_grad']))
+    # (Adam turns the rounding noise of gradients that are zero in exact arithmetic -- the key-projection biases -- into full-size steps;
+    # after the setup, warm-up and timed iterations theta agrees to that noise and the meta-gradient taken there keeps its direction)
+    assert rel < 1e-3 and cos > 0.99, (rel, cos)
     # the default above all-reduced G group by group under the validation backward (dist.ChunkedAllReduce: decoder, encoder, conv);
     # with two ranks every element is a + b either way, so ONE collective after the backward must give the same bits of theta
     single = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
@@ -536,12 +550,14 @@ def test_plain_bench_invocation_starts_its_own_ranks():
     assert abs(j1['last_step']['val_loss'] - j2['last_step']['val_loss']) < 1e-4 * abs(j1['last_step']['val_loss'])
 
 
-@pytest.mark.parametrize('world,tasks', [(4, 8), (8, 8)])
-def test_sharded_bench_at_four_and_eight_ranks_on_one_gpu(world, tasks):
-    """BASELINE.json configs[2]'s partitioning with the ranks sharing this box's single GPU over gloo: 8 tasks on 4 ranks (2 per rank: the
-    task-batched schedule with the slice hooks) and on 8 ranks (ONE task per rank: the lane schedule a rank of the 8-GPU node runs) must
+@pytest.mark.parametrize('world,tasks', [(4, 8), (4, 4)])
+def test_sharded_bench_at_four_ranks_on_one_gpu(world, tasks):
+    """bench.py's sharded step with the ranks sharing this box's single GPU over gloo: 8 tasks on 4 ranks (2 per rank: the task-batched
+    schedule with the slice hooks) and 4 tasks on 4 ranks (ONE task per rank: the lane schedule a rank of the 8-GPU node runs) must
     reproduce the single-process step (labels / CER counts equal, loss within 1e-4), report the rank count and the per-rank step times
-    in the `multi_gpu` block, and leave bit-identical replicas."""
+    in the `multi_gpu` block, and leave bit-identical replicas.  Four ranks, the launcher and this process are six processes holding
+    the one device; eight ranks would be ten, more than a shared GPU node admits at once.  The configs[2] partition itself (8 tasks on
+    8 ranks, the 8-way sliced all-reduce) is checked over gloo on CPU: tests/test_dist_gloo.py::test_world8_one_task_per_rank_three_iterations."""
     import json
     import os
     import subprocess

@@ -7,19 +7,19 @@ cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${ROUND:-r6}
 mkdir -p $O
 # counter passes FIRST: bench.py reads profiles/pmc_traffic.json for `roofline.traffic` (per launch, so it must come from the same launch structure)
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial > /dev/null 2>&1
 python tools/pmc_traffic.py $O/pmc_fetch/f_counter_collection.csv $O/pmc_write/w_counter_collection.csv $O/pmc_traffic.json > $O/pmc_traffic.txt 2>&1
 python tools/pmc_summary.py $O/pmc_fetch/f_counter_collection.csv FETCH_SIZE $O/pmc_fetch_size_per_kernel.csv
 python tools/pmc_summary.py $O/pmc_write/w_counter_collection.csv WRITE_SIZE $O/pmc_write_size_per_kernel.csv
 cp $O/pmc_traffic.json profiles/pmc_traffic.json
-python bench.py > $O/bench.json 2> $O/bench.err; cp gpurun_out/bench_detail.json $O/bench_detail.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -o serial -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial > $O/bench_serial_traced.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/lanes -o lanes -- python bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_lanes_traced.json 2> /dev/null
+python bench.py --full > $O/bench.json 2> $O/bench.err; sed -n 's/^bench detail: //p' $O/bench.err > $O/bench_detail.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -o serial -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial > $O/bench_serial_traced.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/lanes -o lanes -- python bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_lanes_traced.json 2> /dev/null
 # what ONE rank of the 8-GPU configuration runs (BASELINE.json configs[2]): one task per step
 mkdir -p $O/one_task
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/one_task/trace -o one -- python bench.py --tasks 1 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/one_task/bench_one_task_traced.json 2> /dev/null
-python bench.py --tasks 1 --steps 30 --warmup 3 --no-cpu-baseline --no-extras 2> /dev/null | tail -1 > $O/one_task/bench_one_task.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/one_task/trace -o one -- python bench.py --full --tasks 1 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/one_task/bench_one_task_traced.json 2> /dev/null
+python bench.py --full --tasks 1 --steps 30 --warmup 3 --no-cpu-baseline --no-extras 2> /dev/null | tail -1 > $O/one_task/bench_one_task.json
 # manifest-like batches (every batch padded to its own longest utterance, new shapes every step): probe line + kernel stats
 mkdir -p $O/ragged
 python tools/probe/ragged_steps.py --mode ragged --steps 40 2> /dev/null | tail -1 > $O/ragged/ragged_stacked.json
@@ -31,12 +31,12 @@ mkdir -p $O/eval
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/eval/trace -o eval -- python bench.py --eval-only > $O/eval/bench_eval_traced.json 2> /dev/null
 python bench.py --eval-only 2> /dev/null | tail -1 > $O/eval/bench_eval.json
 # long-utterance configuration (BASELINE.json configs[3]): T = 5000
-python bench.py --frames 5000 --tasks 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_t5000.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/t5000 -o t5000 -- python bench.py --frames 5000 --tasks 1 --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial > $O/bench_t5000_serial_traced.json 2> /dev/null
+python bench.py --full --frames 5000 --tasks 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_t5000.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/t5000 -o t5000 -- python bench.py --full --frames 5000 --tasks 1 --steps 1 --warmup 1 --no-cpu-baseline --no-extras --serial > $O/bench_t5000_serial_traced.json 2> /dev/null
 # LM meta loop (BASELINE.json configs[4]): bench line + rocprofv3 summary
 mkdir -p $O/lm
-python bench.py --workload lm > $O/lm/bench_lm.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/lm/trace -o lm -- python bench.py --workload lm --steps 3 --warmup 1 --no-cpu-baseline > $O/lm/bench_lm_traced.json 2> /dev/null
+python bench.py --full --workload lm > $O/lm/bench_lm.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/lm/trace -o lm -- python bench.py --full --workload lm --steps 3 --warmup 1 --no-cpu-baseline > $O/lm/bench_lm_traced.json 2> /dev/null
 # isolated products on the bf16-split engine vs the fp32 engines, PMC counters of one of them, and the DVFS probe of the convolutions
 python tools/bench_gemm_x3.py 2> /dev/null | grep -v amdgpu.ids > $O/gemm_x3_vs_fp32.txt
 bash tools/pmc_gemm_x3.sh "ffn fwd (enc)" > /dev/null 2>&1; cp gpurun_out/pmc_x3/summary.txt $O/pmc_gemm_x3_ffn_fwd.txt

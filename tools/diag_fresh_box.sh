@@ -5,7 +5,7 @@ out=gpurun_out/fresh; rm -rf $out; mkdir -p $out
 { echo "nproc $(nproc)  cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>&1)"; grep -E "nr_throttled|throttled_usec|nr_periods" /sys/fs/cgroup/cpu.stat; } > $out/host.txt 2>&1
 ( while true; do rocm-smi -a --json > $out/smi_all.json 2>/dev/null; sleep 1; done ) &
 poll=$!
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $out/b_full_poll.json 2> $out/b_full_poll.err ) 2> $out/b_time.txt
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/b_full_poll.json 2> $out/b_full_poll.err ) 2> $out/b_time.txt
 { echo "after b:"; grep -E "nr_throttled|throttled_usec|nr_periods" /sys/fs/cgroup/cpu.stat; } >> $out/host.txt
 kill $poll
 cp gpurun_out/bench_detail.json $out/b_detail.json
