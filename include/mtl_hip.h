@@ -451,6 +451,17 @@ int mtl_lstm_stack_fwd(void* stream, const mtl_lstm_stack* layers, float mscale,
 int mtl_lstm_stack_bwd(void* stream, const mtl_lstm_stack* layers, const float* dx_up, float mscale, float* scratch, int T, int B, int H,
                        int NL, void* workspace);
 
+/* ---- LM sequence NLL (csrc/mtl_lstm.hip; utils/lm.py:42-155 LM.evaluate: LM rescoring of finished beam hypotheses) ------------
+ * x (R x H, leading dimension ldx): the top LSTM layer's outputs, rows ordered (t, b) with R = T B; W (V x H), bias (V, nullable):
+ * the vocabulary projection (decoder.weight / decoder.bias); target (R) int64, < 0 = skipped row.
+ * row_nll[r] = logsumexp_v(x_r W_v^T + b_v) - (x_r W_target^T + b_target)  (0 for skipped rows, NaN for a target >= V);
+ * seq_nll[b] (nullable) = sum over t of row_nll[t B + b], in t order.  The R x V logits are never written: one pass over (row tile x
+ * vocabulary split) with exact-fp32 MFMA keeps (max, sum-exp, target logit) per split, a second merges the splits in a fixed order.
+ * No atomics: bitwise reproducible.  ws: mtl_lm_nll_workspace(R, V) bytes of device memory (4-byte aligned). */
+long mtl_lm_nll_workspace(int R, int V);
+int mtl_lm_nll_fwd(void* stream, const float* x, int ldx, const float* W, const float* bias, const long* target, int R, int H, int V,
+                   int B, float* row_nll, float* seq_nll, void* ws, long ws_bytes);
+
 
 /* ---- raw byte helpers on a stream (so that a whole task body consists of library calls only and can be replayed) ---- */
 int mtl_memset_zero(void* stream, void* dst, long bytes);

@@ -121,6 +121,8 @@ SIGNATURES = {
     'mtl_lstm_stack_scratch': (L, [I, I, I, I]),
     'mtl_lstm_stack_fwd': (I, [P, P, F, I, I, I, I, P]),
     'mtl_lstm_stack_bwd': (I, [P, P, P, F, P, I, I, I, I, P]),
+    'mtl_lm_nll_workspace': (L, [I, I]),
+    'mtl_lm_nll_fwd': (I, [P, P, I, P, P, P, I, I, I, I, P, P, P, L]),
     'mtl_memset_zero': (I, [P, P, L]),
     'mtl_memcpy_d2d': (I, [P, P, P, L]),
     'mtl_event_record': (I, [P, P]),

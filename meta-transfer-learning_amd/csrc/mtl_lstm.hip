@@ -744,3 +744,178 @@ int mtl_lstm_layer_bwd(void* stream, const float* dx_up, const unsigned char* ma
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Sequence NLL of the LM's vocabulary projection (LM rescoring of finished beam hypotheses, utils/lm.py:42-155 of the reference):
+// nll[r] = logsumexp_v(x_r . W_v + b_v) - (x_r . W_target + b_target) without ever writing the R x V logits.
+//   stage 1 (lm_nll_partial_kernel): grid (row tiles of 64, vocabulary splits); a workgroup runs its rows against the 64-column blocks
+//            of its split with exact-fp32 MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain), keeps an online (max, sum-exp) per
+//            row, picks up the target logit when its column passes, and writes (max, sum-exp, target logit) per (split, row);
+//   stage 2 (lm_nll_merge_kernel): per row, the splits merged in split order -> row_nll;
+//   stage 3 (lm_nll_seq_kernel): per sequence b, seq_nll[b] = sum over t of row_nll[t B + b] in t order.
+// No atomics and fixed orders throughout: two runs give bit-identical results.
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NLL_RT = 64;            // rows per workgroup
+constexpr int NLL_CT = 64;            // vocabulary columns per block
+constexpr int NLL_KT = 32;            // k depth of one LDS stage
+constexpr int NLL_TARGET_WGS = 512;   // stage-1 workgroups aimed for (two per CU; 1024 measured slower: 215 vs 168 us at H = 200)
+
+struct NllSplit {
+    int splits, blocks_per_split;
+};
+NllSplit nll_split(int R, int V) {
+    const int nblk = (V + NLL_CT - 1) / NLL_CT, rt = (R + NLL_RT - 1) / NLL_RT;
+    int s = (NLL_TARGET_WGS + rt - 1) / rt;
+    s = s < 1 ? 1 : (s > nblk ? nblk : s);
+    const int bps = (nblk + s - 1) / s;
+    return NllSplit{(nblk + bps - 1) / bps, bps};      // every split holds at least one column
+}
+
+__device__ __forceinline__ void nll_merge(float& m, float& s, float m2, float s2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) return;                         // both empty
+    s = s * expf(m - M) + s2 * expf(m2 - M);            // (an empty side has s == 0 and m == -inf: its term is 0)
+    m = M;
+}
+
+__global__ __launch_bounds__(256) void lm_nll_partial_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ W,
+                                                            const float* __restrict__ bias, const long* __restrict__ target, int R,
+                                                            int H, int V, int bps, float* __restrict__ part) {
+    __shared__ float xs[NLL_KT][NLL_RT + 1];            // [k][row]
+    __shared__ float wsm[NLL_KT][NLL_CT + 1];           // [k][column]
+    __shared__ float lt[NLL_RT][NLL_CT + 1];            // the logits of one block
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;            // this wave's 32 x 32 quarter of the 64 x 64 block
+    const int r0 = blockIdx.x * NLL_RT;
+    const int c_begin = blockIdx.y * bps * NLL_CT;
+    const int c_end = min(V, c_begin + bps * NLL_CT);
+    // epilogue ownership: thread (row er, strip q) scans the 16 columns [16 q, 16 q + 16) of every block
+    const int er = tid >> 2, q = tid & 3;
+    const int grow = r0 + er;
+    const long tgt = grow < R ? target[grow] : -1;
+    float m = -INFINITY, s = 0.f, tl = -INFINITY;
+    for (int c0 = c_begin; c0 < c_end; c0 += NLL_CT) {
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < H; k0 += NLL_KT) {
+            __syncthreads();                              // the previous stage's operands (and the previous block's logits) are consumed
+#pragma unroll
+            for (int e = 0; e < NLL_RT * NLL_KT / 256; ++e) {
+                const int idx = tid + 256 * e, kk = idx & (NLL_KT - 1), rr = idx / NLL_KT;
+                const int k = k0 + kk, row = r0 + rr, col = c0 + rr;
+                xs[kk][rr] = (row < R && k < H) ? x[(long)row * ldx + k] : 0.f;
+                wsm[kk][rr] = (col < c_end && k < H) ? W[(long)col * H + k] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < NLL_KT; kk += 4) {
+                float a[2], b[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) a[i] = xs[kk + (lane >> 4)][wr * 32 + i * 16 + (lane & 15)];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) b[j] = wsm[kk + (lane >> 4)][wc * 32 + j * 16 + (lane & 15)];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+        // C/D map of the 16x16 form: column lane & 15, row 4 (lane >> 4) + register
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) lt[wr * 32 + i * 16 + 4 * (lane >> 4) + g][wc * 32 + j * 16 + (lane & 15)] = acc[i][j][g];
+        __syncthreads();
+        float v[16], mb = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int col = c0 + 16 * q + u;
+            v[u] = col < c_end ? lt[er][16 * q + u] + (bias ? bias[col] : 0.f) : -INFINITY;
+            mb = fmaxf(mb, v[u]);
+            if (col == tgt) tl = v[u];
+        }
+        if (mb != -INFINITY) {
+            const float M = fmaxf(m, mb);
+            float sb = 0.f;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) sb += expf(v[u] - M);      // (masked columns: exp(-inf) = 0)
+            s = s * expf(m - M) + sb;
+            m = M;
+        }
+    }
+    // the four strips of a row sit in four adjacent lanes: butterfly merge (the same value in all four: both operations commute)
+#pragma unroll
+    for (int o = 1; o <= 2; o <<= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64), t2 = __shfl_xor(tl, o, 64);
+        nll_merge(m, s, m2, s2);
+        tl = fmaxf(tl, t2);                               // at most one strip holds the target (-inf elsewhere)
+    }
+    if (q == 0 && grow < R) {
+        float* p = part + ((long)blockIdx.y * R + grow) * 3;
+        p[0] = m, p[1] = s, p[2] = tl;
+    }
+}
+
+__global__ __launch_bounds__(256) void lm_nll_merge_kernel(const float* __restrict__ part, const long* __restrict__ target, int R, int V,
+                                                          int splits, float* __restrict__ row_nll) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const long tgt = target[r];
+    if (tgt < 0) {
+        row_nll[r] = 0.f;                                 // skipped row (padding)
+        return;
+    }
+    float m = -INFINITY, s = 0.f, tl = -INFINITY;
+    for (int k = 0; k < splits; ++k) {
+        const float* p = part + ((long)k * R + r) * 3;
+        nll_merge(m, s, p[0], p[1]);
+        tl = fmaxf(tl, p[2]);
+    }
+    row_nll[r] = (tgt < V && tl != -INFINITY) ? (m + logf(s)) - tl : __int_as_float(0x7fc00000);   // target out of range: NaN
+}
+
+__global__ __launch_bounds__(256) void lm_nll_seq_kernel(const float* __restrict__ row_nll, int T, int B, float* __restrict__ seq_nll) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    float acc = 0.f;
+    for (int t = 0; t < T; ++t) acc += row_nll[(long)t * B + b];
+    seq_nll[b] = acc;
+}
+
+}  // namespace
+
+extern "C" {
+
+long mtl_lm_nll_workspace(int R, int V) {
+    if (R <= 0 || V <= 0) return 0;
+    return (long)nll_split(R, V).splits * R * 3 * 4;
+}
+
+int mtl_lm_nll_fwd(void* stream, const float* x, int ldx, const float* W, const float* bias, const long* target, int R, int H, int V,
+                   int B, float* row_nll, float* seq_nll, void* ws, long ws_bytes) {
+    if (!x || !W || !target || !row_nll || !ws || R <= 0 || H <= 0 || V <= 0 || B <= 0 || R % B != 0 || ldx < H) return MTL_EINVAL;
+    if (ws_bytes < mtl_lm_nll_workspace(R, V) || (reinterpret_cast<uintptr_t>(ws) & 3)) return MTL_EINVAL;
+    const NllSplit sp = nll_split(R, V);
+    hipStream_t s = as_stream(stream);
+    float* part = static_cast<float*>(ws);
+    hipLaunchKernelGGL(lm_nll_partial_kernel, dim3((R + NLL_RT - 1) / NLL_RT, sp.splits), dim3(256), 0, s, x, ldx, W, bias, target, R, H,
+                       V, sp.blocks_per_split, part);
+    MTL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lm_nll_merge_kernel, dim3((R + 255) / 256), dim3(256), 0, s, part, target, R, V, sp.splits, row_nll);
+    MTL_CHECK_LAUNCH();
+    if (seq_nll) {
+        hipLaunchKernelGGL(lm_nll_seq_kernel, dim3((B + 255) / 256), dim3(256), 0, s, row_nll, R / B, B, seq_nll);
+        MTL_CHECK_LAUNCH();
+    }
+    return MTL_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@ contract of utils/data_loader.py:191-195 and the batch layout returned by `Spect
 """
 import csv
 import json
+import unicodedata
 
 import numpy as np
 import torch
@@ -53,6 +54,38 @@ def synthetic_vocab(size):
         vocab.add_token(ch)
         vocab.add_label(ch)
     return vocab
+
+
+def is_chinese_char(cc):
+    """utils/data.py:60-68: a character of Unicode category 'Lo' (other letter) counts as Chinese"""
+    return unicodedata.category(cc) == 'Lo'
+
+
+def is_contain_chinese_word(seq):
+    """utils/data.py:70-81"""
+    return any(is_chinese_char(c) for c in seq)
+
+
+def get_word_segments_per_language(seq):
+    """utils/data.py:84-127: split `seq` on single spaces and group consecutive words by language (a word holding any Chinese
+    character is Chinese) -> list of segments, each the space-joined words of one run ('' words from double spaces included)"""
+    cur_lang = -1                       # 0 English, 1 Chinese
+    temp_words = ''
+    word_segments = []
+    for word in seq.split(' '):
+        lang = 1 if is_contain_chinese_word(word) else 0
+        if cur_lang == -1:
+            temp_words = word
+        elif cur_lang != lang:
+            word_segments.append(temp_words)
+            temp_words = word
+        else:
+            if temp_words != '':
+                temp_words += ' '
+            temp_words += word
+        cur_lang = lang
+    word_segments.append(temp_words)
+    return word_segments
 
 
 def read_manifest(path):

@@ -1497,13 +1497,16 @@ class PassEngine:
             ent.run()
         return ys[1:]
 
-    def beam_decode(self, theta, mem_row, T4, start_token, beam_width, nbest, tgt_max_len, num_words, eos_id=EOS_ID, c_weight=1.0):
+    def beam_decode(self, theta, mem_row, T4, start_token, beam_width, nbest, tgt_max_len, num_words, eos_id=EOS_ID, c_weight=1.0,
+                    ended_out=None):
         """Decoder.beam_search (modules/decoder.py:187-291, no LM rescoring) for ONE utterance: the host keeps the reference's
         hypothesis bookkeeping verbatim in behaviour (expansion order, stable sorts, cumulative truncation to the beam, EOS
         forced at step T' - 1, final_score = score + sqrt(num_words) * c_weight, fp32 score arithmetic); the device runs one
         K/V-cached decoder step for all live hypotheses per iteration (caches re-ordered by parent) and returns the last
         position's logits and log-sum-exp.  num_words(yseq) -> int is the caller's word counter (it needs the vocabulary).
-        -> list of (yseq incl. start token and EOS, final_score) sorted best first, at most nbest."""
+        -> list of (yseq incl. start token and EOS, final_score) sorted best first, at most nbest.
+        ended_out: a list that receives EVERY ended hypothesis in the order it ended, as dicts with 'score' (fp32, the decoder's
+        log-probability) and 'yseq' (the caller's LM rescoring re-ranks them, modules/decoder.py:248-256)."""
         import numpy as np
         W = int(beam_width)
         steps = int(tgt_max_len)
@@ -1576,6 +1579,8 @@ class PassEngine:
             hyps = live
             if not hyps:
                 break
+        if ended_out is not None:
+            ended_out.extend(dict(score=h['score'], yseq=list(h['yseq'])) for h in ended)
         out = sorted(ended, key=lambda x: x['final_score'], reverse=True)[:min(len(ended), int(nbest))]
         return [(h['yseq'], float(h['final_score'])) for h in out]
 

@@ -128,7 +128,7 @@ class LMEngine:
         if int(self.sync_ws[1]) != 0:
             self.sync_ws[1] = 0
             raise RuntimeError('mtl_lstm: a grid-wide wait of a persistent LSTM launch timed out; its results are invalid '
-                               '(MTL_LSTM_STACK=0 / MTL_LSTM_PERSISTENT=0 select the per-layer / per-step launches)')
+                               '(LMEngine.stacked = False / LMEngine.persistent = False select the per-layer / per-step launches)')
 
     def buf(self, name, shape, dtype=torch.float32):
         key = (name, tuple(int(v) for v in shape), dtype)
@@ -162,6 +162,54 @@ class LMEngine:
     def forward(self, theta, x, y, hidden, dropout_p=0.0):
         """x (T, B) int64, y (T*B) int64 or None, hidden (h, c) each (L, B, H).  -> dict(logits (T*B, V), loss (1,) or None,
         hidden (detached new state))."""
+        rec = self._recurrent(theta, x, hidden, dropout_p)
+        m, lib, st, Lo = self.m, self.lib, self.stream, self.L
+        T, B, xin = rec['T'], rec['B'], rec['last']
+        R, H, V = T * B, m.nhid, m.ntoken
+        P = theta.data_ptr()
+        o = lambda n: P + 4 * Lo.off(n)
+        logits = self.buf('logits', (R, V))
+        self.gemm(0, 1, R, V, H, xin.data_ptr(), H, o('decoder.weight'), H, logits.data_ptr(), V, bias=o('decoder.bias'))
+        loss = None
+        if y is not None:
+            gold = self.buf('gold', (R,), torch.int64)
+            gold.copy_(y.detach().reshape(-1).to(torch.int64), non_blocking=True)
+            lse, hyp, rowloss, loss = self.buf('lse', (R,)), self.buf('hyp', (R,), torch.int64), self.buf('rowloss', (R,)), self.buf('loss', (1,))
+            check(lib.mtl_ce_argmax_fwd(st, logits.data_ptr(), gold.data_ptr(), R, V, V, -1, 0.0, R, None, lse.data_ptr(), hyp.data_ptr(),
+                                        rowloss.data_ptr(), loss.data_ptr()), 'ce_fwd')     # nn.CrossEntropyLoss(): mean over all T*B rows
+        self.saved = dict(theta=theta, **rec)
+        return dict(logits=logits, loss=loss, hidden=(rec['hn'].clone(), rec['cn'].clone()))
+
+    def sequence_nll(self, theta, ids, targets):
+        """Summed next-word NLL of a ragged batch (LM rescoring, utils/lm.py:112-136 of the reference, batched): ids (T, B) int64,
+        targets (T, B) int64 with -1 after a sequence's end.  Eval-mode forward from the zero state (the LSTM is causal: the padding
+        after a sequence's end cannot change its valid positions), then ONE fused vocabulary projection + log-sum-exp
+        (mtl_lm_nll_fwd; the T B x V logits are never written).  -> seq_nll (B,) fp32 on the device.  Reuses forward()'s buffers:
+        a pending backward() is invalidated."""
+        m, lib = self.m, self.lib
+        T, B = int(ids.shape[0]), int(ids.shape[1])
+        if tuple(targets.shape) != (T, B):
+            raise ValueError('targets must have the shape of ids (T, B)')
+        R, H, V, NL = T * B, m.nhid, m.ntoken, m.nlayers
+        self.saved = None
+        zero = self.buf('nll_h0', (NL, B, H))
+        zero.zero_()
+        rec = self._recurrent(theta, ids, (zero, zero), 0.0)
+        self.saved = None
+        tgt = self.buf('nll_tgt', (R,), torch.int64)
+        tgt.copy_(targets.detach().reshape(-1).to(torch.int64), non_blocking=True)
+        row, seq = self.buf('nll_row', (R,)), self.buf('nll_seq', (B,))
+        need = int(lib.mtl_lm_nll_workspace(R, V))
+        ws = self.ws if need <= self.ws.numel() * 4 else self.buf('nll_ws', ((need + 3) // 4,))
+        P = theta.data_ptr()
+        check(lib.mtl_lm_nll_fwd(self.stream, rec['last'].data_ptr(), H, P + 4 * self.L.off('decoder.weight'), P + 4 * self.L.off('decoder.bias'),
+                                 tgt.data_ptr(), R, H, V, B, row.data_ptr(), seq.data_ptr(), ws.data_ptr(), ws.numel() * 4), 'mtl_lm_nll_fwd')
+        self.check_handoff()          # the caller ranks hypotheses by these values
+        return seq.clone()
+
+    def _recurrent(self, theta, x, hidden, dropout_p):
+        """the recurrent half of forward(): embedding (+ dropout) and the LSTM stack over x (T, B) from `hidden` -> dict with the top
+        layer's (dropped) output `last` (T B, H) and what backward() needs"""
         m, lib, st, Lo = self.m, self.lib, self.stream, self.L
         T, B = int(x.shape[0]), int(x.shape[1])
         R, H, E, V, NL = T * B, m.nhid, m.ninp, m.ntoken, m.nlayers
@@ -248,17 +296,7 @@ class LMEngine:
         for l in range(NL):
             hn[l].copy_(layers[l]['hall'][T])
             cn[l].copy_(layers[l]['call'][T])
-        logits = self.buf('logits', (R, V))
-        self.gemm(0, 1, R, V, H, xin.data_ptr(), H, o('decoder.weight'), H, logits.data_ptr(), V, bias=o('decoder.bias'))
-        loss = None
-        if y is not None:
-            gold = self.buf('gold', (R,), torch.int64)
-            gold.copy_(y.detach().reshape(-1).to(torch.int64), non_blocking=True)
-            lse, hyp, rowloss, loss = self.buf('lse', (R,)), self.buf('hyp', (R,), torch.int64), self.buf('rowloss', (R,)), self.buf('loss', (1,))
-            check(lib.mtl_ce_argmax_fwd(st, logits.data_ptr(), gold.data_ptr(), R, V, V, -1, 0.0, R, None, lse.data_ptr(), hyp.data_ptr(),
-                                        rowloss.data_ptr(), loss.data_ptr()), 'ce_fwd')     # nn.CrossEntropyLoss(): mean over all T*B rows
-        self.saved = dict(theta=theta, T=T, B=B, layers=layers, last=xin, m_emb=m_emb, sc=sc, ids=ids, chains=chains, stacked=stacked, arena=arena)
-        return dict(logits=logits, loss=loss, hidden=(hn.clone(), cn.clone()))
+        return dict(T=T, B=B, layers=layers, last=xin, m_emb=m_emb, sc=sc, ids=ids, chains=chains, stacked=stacked, arena=arena, hn=hn, cn=cn)
 
     def backward(self, grad, scale=1.0):
         """grad (flat) += scale * dLoss/dtheta of the last forward (truncated BPTT over the window: no gradient into the incoming

@@ -315,9 +315,12 @@ class Transformer(nn.Module):
         from PassEngine.greedy_decode (K/V-cached, device-resident token feedback); beam_search=True runs
         PassEngine.beam_decode per utterance with args.beam_width / args.beam_nbest / args.tgt_max_len like the reference
         (all n-best strings of all utterances, concatenated; falls back to greedy when the best hypothesis is empty).
-        LM rescoring is not on the accelerated path."""
-        if lm_rescoring:
-            raise NotImplementedError('LM rescoring is outside the accelerated path')
+        lm_rescoring=True with beam_search=True (modules/decoder.py:248-256): every ended hypothesis of the batch is scored by the
+        word-level LM `lm` (lmscore.LM) in ONE device pass after the search, final_score = score + lm_weight * (lm_score - 2 oov) +
+        sqrt(LM words + 1) * c_weight, and each utterance's hypotheses are re-sorted (stable) by it; ignored by the greedy search."""
+        if lm_rescoring and beam_search and lm is None:
+            raise ValueError('lm_rescoring=True needs lm= (an lmscore.LM)')
+        rescoring = bool(lm_rescoring and beam_search)
         eng = self._need_engine()
         was_training = self.training
         self.eval()
@@ -335,13 +338,23 @@ class Transformer(nn.Module):
             strs_beam = None
             if beam_search:
                 mem = mem.clone()                                              # the decode buffers live in the same arena
-                ids_nbest, strs_beam = [], []
+                ids_nbest, ended = [], []
                 for b in range(B):
+                    ended.append([] if rescoring else None)
                     res = eng.beam_decode(self._theta, mem.data_ptr() + 4 * b * T4 * eng.hp.d, T4, start, args.beam_width,
-                                          args.beam_nbest, args.tgt_max_len, self._num_words, self.vocab.EOS_ID, c_weight)
-                    for yseq, _score in res:
-                        ids_nbest.append(yseq)
-                        strs_beam.append(self._post_process_hyp(yseq))
+                                          args.beam_nbest, args.tgt_max_len, self._num_words, self.vocab.EOS_ID, c_weight,
+                                          ended_out=ended[b])
+                    if not rescoring:
+                        ids_nbest.extend(yseq for yseq, _score in res)
+                if rescoring:
+                    from .lmscore import rescore
+                    rescore([h for utt in ended for h in utt], lm, self.vocab, lm_weight, c_weight)       # one LM pass for the batch
+                    self.last_beam_scores = []
+                    for utt in ended:
+                        best = sorted(utt, key=lambda h: h['final_score'], reverse=True)[:min(len(utt), int(args.beam_nbest))]
+                        ids_nbest.extend(h['yseq'] for h in best)
+                        self.last_beam_scores.extend(float(h['final_score']) for h in best)
+                strs_beam = [self._post_process_hyp(yseq) for yseq in ids_nbest]
                 if len(strs_beam) == 0 or len(strs_beam[0].strip()) == 0:
                     strs_beam = None                                           # ">>>>>>> switch to greedy" (:190-196)
             if strs_beam is None:
