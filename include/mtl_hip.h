@@ -462,6 +462,46 @@ long mtl_lm_nll_workspace(int R, int V);
 int mtl_lm_nll_fwd(void* stream, const float* x, int ldx, const float* W, const float* bias, const long* target, int R, int H, int V,
                    int B, float* row_nll, float* seq_nll, void* ws, long ws_bytes);
 
+/* ---- device-resident beam search (csrc/mtl_beam.hip; modules/decoder.py:187-291 Decoder.beam_search) --------------------------
+ * A chunk of U utterances is searched at once: W hypothesis rows per utterance, row u W + r of every (U W, ...) operand.
+ * Limits (anything beyond is refused with -22): 1 <= W <= MTL_BEAM_MAX_W, W <= V <= MTL_BEAM_MAX_V, 1 <= S <= MTL_BEAM_MAX_S
+ * positions, U <= MTL_BEAM_MAX_U, at most MTL_BEAM_MAX_CACHES caches per gather.
+ *
+ * mtl_beam_rank: what modules/decoder.py:215-280 does between two decoder steps, for position i of all U utterances in ONE launch
+ * (a workgroup per utterance).  logits (U W, V) and lse (U W) = log-sum-exp of each row (mtl_ce_argmax_fwd's `lse`).  Selection rule:
+ *   - live row r (row order) offers the W largest  local = logit - lse  (fp32) of its row, largest first, equal values resolving to the
+ *     LOWER vocabulary id; candidate score = fp32(score_r + local);
+ *   - the W best of the n W candidates survive, equal scores resolving to the EARLIER (row, rank) pair (a stable descending sort of the
+ *     candidates in (row, rank) order, cut at W -- equal to the reference's cumulative sorted(...)[:W]); survivors keep that order;
+ *   - at i == T4 - 1 every survivor ends with a forced EOS appended behind its token;
+ *   - survivors ending in EOS are appended to the utterance's ended list (survivor order), the others become live rows 0..n'-1.
+ * state: mtl_beam_state_words(U, W, S) int32 words (fp32 values as their bit patterns):
+ *   hdr   [U][4]        live rows n | done flag | ended entries | reserved      (start of a search: 1, 0, 0, 0)
+ *   score [U][W]   f32  score of live row r                                     (start: score[u][0] = 0)
+ *   bp    [U][S][W]     bp[u][i][r'] = live row BEFORE position i that live row r' AFTER position i continues
+ *   tk    [U][S][W]     tk[u][i][r'] = the token appended at position i
+ *   ended [U][S W][5]   position | score (f32) | live row before that position | token | 1 = EOS forced behind the token, 0 = token is the EOS
+ * so the sequence of live row r before position i is  seq(i, r) = seq(i - 1, bp[i-1][r]) + [tk[i-1][r]],  seq(0, 0) = [start token],
+ * and an ended entry is  seq(position, row) + [token] (+ [EOS] when forced).
+ * Outputs for position i + 1: tok (U W) int64 = the live rows' tokens (rows n'.. are fed eos_id), parent (U W) int32 = the GLOBAL row
+ * u W + bp whose caches row u W + r' continues (rows n'..: the utterance's row 0).  An utterance is done (flag set) when no live row is
+ * left; the kernel returns at once for a done utterance and leaves its state, tok and parent untouched (the step that finishes it
+ * writes the identity into its parent rows).
+ *
+ * mtl_beam_gather: caches[c][r, :t] <- caches[c][parent[r], :t] for c < ncache, with `parent` read from device memory.  caches_dev:
+ * DEVICE table of ncache pointers to (rows, S', width) fp32 caches, 16-byte aligned, row_stride floats between two rows (>= t width;
+ * width and row_stride multiples of 4).  Never permutes in place: the moved rows go to tmp (>= ncache rows t width floats, 16-byte
+ * aligned) and are copied back by a second launch; rows with parent[r] == r are not touched. */
+#define MTL_BEAM_MAX_W 8
+#define MTL_BEAM_MAX_V (1 << 20)
+#define MTL_BEAM_MAX_S 4096
+#define MTL_BEAM_MAX_U 64
+#define MTL_BEAM_MAX_CACHES 64
+long mtl_beam_state_words(int U, int W, int S); /* -22 beyond the limits */
+int mtl_beam_rank(void* stream, const float* logits, const float* lse, int* state, long* tok, int* parent, int i, int T4, int U, int W,
+                  int V, int S, int eos_id);
+int mtl_beam_gather(void* stream, float* const* caches_dev, int ncache, const int* parent, float* tmp, long tmp_floats, int rows, int t,
+                    int width, long row_stride);
 
 /* ---- raw byte helpers on a stream (so that a whole task body consists of library calls only and can be replayed) ---- */
 int mtl_memset_zero(void* stream, void* dst, long bytes);

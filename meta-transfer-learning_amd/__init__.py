@@ -6,11 +6,12 @@ from . import _lib  # noqa: F401
 from .data import (Vocab, SyntheticTask, ManifestTaskDataset, SpectrogramDataset, BucketingSampler, AudioDataLoader, SpectrogramFrontEnd, load_vocab, load_wav_pcm16, synthetic_vocab,  # noqa: F401
                    synth_batch, is_chinese_char, is_contain_chinese_word, get_word_segments_per_language)
 from .functions import (init_transformer_model, save_meta_model, load_meta_model, save_joint_model, load_joint_model,  # noqa: F401
-                        post_process)
-from .metrics import calculate_metrics, calculate_cer  # noqa: F401
+                        post_process, compute_num_params)
+from .metrics import calculate_metrics, calculate_cer, calculate_wer, calculate_cer_en_zh  # noqa: F401
 from .model import Transformer, Encoder, Decoder  # noqa: F401
 from .trainer import TransientTrainer, JointTrainer, FlatAdam, FlatSGD  # noqa: F401
 from . import dist  # noqa: F401
 from . import hostenv  # noqa: F401
 from . import lm  # noqa: F401
 from .lmscore import LM, calculate_lm_score, lm_string  # noqa: F401
+from .testset import evaluate_test_set  # noqa: F401

@@ -123,6 +123,9 @@ SIGNATURES = {
     'mtl_lstm_stack_bwd': (I, [P, P, P, F, P, I, I, I, I, P]),
     'mtl_lm_nll_workspace': (L, [I, I]),
     'mtl_lm_nll_fwd': (I, [P, P, I, P, P, P, I, I, I, I, P, P, P, L]),
+    'mtl_beam_state_words': (L, [I, I, I]),
+    'mtl_beam_rank': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I]),
+    'mtl_beam_gather': (I, [P, P, I, P, P, L, I, I, I, L]),
     'mtl_memset_zero': (I, [P, P, L]),
     'mtl_memcpy_d2d': (I, [P, P, P, L]),
     'mtl_event_record': (I, [P, P]),

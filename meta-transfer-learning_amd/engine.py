@@ -100,8 +100,13 @@ _FULL = {'q': 'query', 'k': 'key', 'v': 'value'}
 class _DecodeSession:
     """See PassEngine.decode_session."""
 
-    def __init__(self, eng, theta, mem, B, T4, S, shared_memory):
+    def __init__(self, eng, theta, mem, B, T4, S, shared_memory, groups=1):
         self.eng, self.B, self.T4, self.S = eng, B, T4, S
+        # groups > 1 (batched beam search): the B rows are `groups` utterances of B / groups hypothesis rows each, every utterance's
+        # rows sharing ITS encoder memory -- mem is (groups, T4, d)
+        self.groups = int(groups) if shared_memory else 1
+        if B % self.groups:
+            raise ValueError('rows do not divide into %d groups' % self.groups)
         hp = eng.hp
         d, r, h, dk, dv, V = hp.d, hp.r, hp.h, hp.dk, hp.dv, hp.V
         hk, hv = h * dk, h * dv
@@ -146,7 +151,7 @@ class _DecodeSession:
         else:
             self.kc = [buf('g.kc%d' % i, (B, S, hk)) for i in range(hp.n_dec)]
             self.vc = [buf('g.vc%d' % i, (B, S, hv)) for i in range(hp.n_dec)]
-        Bm = 1 if shared_memory else B
+        Bm = self.groups if shared_memory else B
         self.cross_stride = 0 if shared_memory else T4
         self.ck = [buf('g.ck%d' % i, (Bm * T4, hk)) for i in range(hp.n_dec)]
         self.cv = [buf('g.cv%d' % i, (Bm * T4, hv)) for i in range(hp.n_dec)]
@@ -188,6 +193,19 @@ class _DecodeSession:
                                            ldS, None, 1.0, None), 'softmax')
         eng.gemm(0, 0, 1, dv, kv_rows, self.Sc.data_ptr(), ldS, vbuf, hv, out, hv, batch=B * h, H=h, sA=(h * ldS, ldS),
                  sB=(kv_stride, dv), sC=(hv, dv))
+
+    def _attend_groups(self, q, kbuf, vbuf, kv_rows, out):
+        # cross-attention of `groups` utterances with W = B / groups query rows each: the same two strided-batch products and softmax
+        # as _attend, batch = (utterance, head) with M = W rows per item instead of (row, head) with M = 1
+        eng, hp, B, U = self.eng, self.eng.hp, self.B, self.groups
+        h, dk, dv, W = hp.h, hp.dk, hp.dv, self.B // self.groups
+        hk, hv, ldS = h * dk, h * dv, self.ldS
+        eng.gemm(0, 1, W, kv_rows, dk, q, hk, kbuf, hk, self.Sc.data_ptr(), h * ldS, batch=U * h, H=h, sA=(W * hk, dk),
+                 sB=(kv_rows * hk, dk), sC=(W * h * ldS, ldS))
+        check(eng.lib.mtl_softmax_mask_fwd(eng.stream, self.Sc.data_ptr(), None, 0, 1.0 / float(hp.temperature), B, h, 1, kv_rows,
+                                           ldS, None, 1.0, None), 'softmax')
+        eng.gemm(0, 0, W, dv, kv_rows, self.Sc.data_ptr(), h * ldS, vbuf, hv, out, hv, batch=U * h, H=h, sA=(W * h * ldS, ldS),
+                 sB=(kv_rows * hv, dv), sC=(W * hv, dv))
 
     def step(self, t, tok_ptr):
         """Feed the B tokens at device address tok_ptr as position t; leaves the logits of that position in self.logits."""
@@ -232,6 +250,8 @@ class _DecodeSession:
                 check(lib.mtl_attn_fwd(eng.stream, self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), hk, hk, hv,
                                        self.klen_cross.data_ptr(), 0, 1.0 / float(hp.temperature), B, hp.h, 1, T4, hp.dk, hp.dv, None, 0, 1.0,
                                        self.to.data_ptr(), hv, self.lse.data_ptr()), 'mtl_attn_fwd')
+            elif self.groups > 1:
+                self._attend_groups(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.to.data_ptr())
             else:
                 self._attend(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.cross_stride * hk, self.to.data_ptr())
             if self.fast:
@@ -271,6 +291,54 @@ class _DecodeSession:
         idx = torch.tensor(rows, dtype=torch.int64, device=self.logits.device)
         for c in self.kc + self.vc:
             c[:, :t] = c.index_select(0, idx)[:, :t]
+
+    def gather_tables(self):
+        """device tables of the K / V cache addresses for mtl_beam_gather: [(table, caches, width)], one entry when h d_k = h d_v"""
+        eng, hp = self.eng, self.eng.hp
+        hk, hv = hp.h * hp.dk, hp.h * hp.dv
+        sets = [(self.kc + self.vc, hk)] if hk == hv else [(self.kc, hk), (self.vc, hv)]
+        out = []
+        for j, (caches, width) in enumerate(sets):
+            tab = eng.buf('g.tab%d' % j, (len(caches),), torch.int64)
+            tab.copy_(torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64))
+            out.append((tab, len(caches), width))
+        self.gtmp = eng.buf('g.gtmp', (max(n for _t, n, _w in out) * self.B * self.S * max(hk, hv),))
+        return out
+
+    def gather(self, tables, parent_ptr, t):
+        """caches[r, :t] <- caches[parent[r], :t] for every layer, parent (B,) int32 in device memory (reorder() without the host)"""
+        eng = self.eng
+        for tab, n, width in tables:
+            check(eng.lib.mtl_beam_gather(eng.stream, tab.data_ptr(), n, parent_ptr, self.gtmp.data_ptr(), self.gtmp.numel(), self.B, t, width,
+                                          self.S * width), 'mtl_beam_gather')
+
+
+def beam_unpack(state, U, W, S, start_token, eos_id):
+    """host side of mtl_beam_rank's state (include/mtl_hip.h): per utterance the ended hypotheses in the order they ended, as dicts
+    with 'score' (numpy fp32) and 'yseq' (start token ... EOS), rebuilt from the back-pointer and token tables"""
+    import numpy as np
+    state = np.ascontiguousarray(state, dtype=np.int32)
+    o_bp = 4 * U + U * W
+    o_tk = o_bp + U * S * W
+    o_en = o_tk + U * S * W
+    bp = state[o_bp:o_tk].reshape(U, S, W)
+    tk = state[o_tk:o_en].reshape(U, S, W)
+    en = state[o_en:o_en + 5 * U * S * W].reshape(U, S * W, 5)
+    out = []
+    for u in range(U):
+        def seq(i, r):
+            rev = []
+            while i > 0:
+                rev.append(int(tk[u, i - 1, r]))
+                r = int(bp[u, i - 1, r])
+                i -= 1
+            return [int(start_token)] + rev[::-1]
+        ended = []
+        for e in en[u, :int(state[4 * u + 2])]:
+            yseq = seq(int(e[0]), int(e[2])) + [int(e[3])] + ([int(eos_id)] if e[4] else [])
+            ended.append(dict(score=e[1:2].view(np.float32)[0], yseq=yseq))
+        out.append(ended)
+    return out
 
 
 CENSUS_SLOTS = 9    # bound slots of the h2 operands: 0 y1, 1 p1, 2 y5, 3 dp2, 4 dy5, 5 dp1, 6 p2, (7: weights, not counted) 8 de0
@@ -1448,11 +1516,11 @@ class PassEngine:
                     frames=meta.get('frames'))
 
     # ---------------------------------------------------------------- greedy decoding
-    def decode_session(self, theta, mem, B, T4, S, shared_memory=False):
+    def decode_session(self, theta, mem, B, T4, S, shared_memory=False, groups=1):
         """K/V-cached incremental decoder over `B` hypothesis rows and up to `S` positions (greedy and beam search share it).
         mem: device pointer of the encoder output, (B, T4, d) -- or (1, T4, d) with shared_memory=True, when all rows are
         hypotheses of ONE utterance (beam search) and address the same cross-attention keys / values with batch stride 0."""
-        return _DecodeSession(self, theta, mem, B, T4, S, shared_memory)
+        return _DecodeSession(self, theta, mem, B, T4, S, shared_memory, groups)
 
     def greedy_decode(self, theta, mem, B, T4, start_token, max_steps=300):
         """Decoder.greedy_search (modules/decoder.py:131-185) on the device: max_steps arg-max steps from `start_token`,
@@ -1583,6 +1651,112 @@ class PassEngine:
             ended_out.extend(dict(score=h['score'], yseq=list(h['yseq'])) for h in ended)
         out = sorted(ended, key=lambda x: x['final_score'], reverse=True)[:min(len(ended), int(nbest))]
         return [(h['yseq'], float(h['final_score'])) for h in out]
+
+    BEAM_ROWS = 16      # rows of a batched beam-search session: U = BEAM_ROWS // W utterances per chunk (DESIGN.md "Test-set evaluation")
+    BEAM_POLL = 4       # positions between two reads of the done flags
+
+    def beam_chunk(self, beam_width):
+        """utterances per chunk of beam_decode_batch: U W <= BEAM_ROWS keeps every product of a step on the engine (and within the one
+        row tile) that the W-row session of beam_decode uses"""
+        return max(1, self.BEAM_ROWS // int(beam_width))
+
+    def beam_decode_batch(self, theta, mem_ptr, U, T4, start_token, beam_width, nbest, tgt_max_len, num_words, eos_id=EOS_ID, c_weight=1.0,
+                          ended_out=None, chunk=None):
+        """Decoder.beam_search for U utterances with the hypothesis bookkeeping on the device: per position one K/V-cached decoder step
+        for the rows of a whole chunk of utterances, the log-sum-exp, mtl_beam_rank (candidates, stable global top-W, forced EOS, split
+        into ended / live, back-pointers) and mtl_beam_gather (caches re-ordered by the parents the ranking left in device memory).
+        The host reads no logits: every BEAM_POLL positions it reads the chunk's done flags (one stream synchronisation on a pinned
+        copy), and after the search the ended lists and back-pointer tables in one copy, from which it rebuilds every yseq.
+        mem_ptr: device address of the (U, T4, d) encoder output.  -> per utterance the list beam_decode returns ((yseq, final_score),
+        best first, at most nbest); final_score = fp32(score + fp32(sqrt(num_words(yseq)) c_weight)) and the n-best sort stay on the
+        host (num_words needs the vocabulary's strings).  ended_out: a list of U lists; list u receives every ended hypothesis of
+        utterance u in the order it ended, as dicts with 'score' (fp32) and 'yseq'.  If tgt_max_len < T4 the loop ends without the
+        forced EOS and unended hypotheses are dropped, as in the reference.  chunk: utterances per session (default beam_chunk(W))."""
+        import numpy as np
+        W, steps, U = int(beam_width), int(tgt_max_len), int(U)
+        if steps > self.pe_dec.shape[0] or W < 1 or steps < 1 or U < 1 or (ended_out is not None and len(ended_out) != U):
+            raise ValueError('bad beam search arguments')
+        Uc_max = self.beam_chunk(W) if chunk is None else max(1, int(chunk))
+        results = []
+        for u0 in range(0, U, Uc_max):
+            Uc = min(Uc_max, U - u0)
+            got = self._beam_chunk_search(theta, int(mem_ptr) + 4 * u0 * T4 * self.hp.d, Uc, T4, int(start_token), W, steps, int(eos_id))
+            for u, ended in enumerate(got):
+                for h in ended:
+                    h['final_score'] = np.float32(h['score'] + np.float32(math.sqrt(num_words(h['yseq'])) * c_weight))
+                if ended_out is not None:
+                    ended_out[u0 + u].extend(dict(score=h['score'], yseq=list(h['yseq'])) for h in ended)
+                out = sorted(ended, key=lambda x: x['final_score'], reverse=True)[:min(len(ended), int(nbest))]
+                results.append([(h['yseq'], float(h['final_score'])) for h in out])
+        return results
+
+    def _beam_chunk_search(self, theta, mem, Uc, T4, start_token, W, steps, eos_id):
+        """one chunk of beam_decode_batch -> per utterance the ended hypotheses (dicts: score fp32, yseq) in the order they ended"""
+        import numpy as np
+        lib_, V, B = self.lib, self.hp.V, Uc * W
+        npos = min(steps, T4)                                     # (EOS is forced at position T4 - 1: no position beyond it)
+        words = lib_.mtl_beam_state_words(Uc, W, npos)            # the tables cover the positions that can run, not tgt_max_len
+        if words < 0:
+            raise ValueError('beam search beyond the limits of mtl_beam_rank (include/mtl_hip.h)')
+        ses = self.decode_session(theta, mem, B, T4, steps, shared_memory=True, groups=Uc)
+        tables = ses.gather_tables()
+        state = self.buf('bb.state', (words,), torch.int32)
+        toks = self.buf('bb.tok', (B,), torch.int64)
+        parent = self.buf('bb.par', (B,), torch.int32)
+        hyp_buf = self.buf('g.hyp', (B,), torch.int64)
+        head = 4 * Uc + Uc * W                                    # hdr + score: all a search needs initialised
+        init = np.zeros(head, dtype=np.int32)
+        init[0:4 * Uc:4] = 1                                      # one live row (the start token) with score 0
+        state[:head].copy_(torch.from_numpy(init))
+        t0 = np.full((Uc, W), eos_id, dtype=np.int64)
+        t0[:, 0] = start_token
+        toks.copy_(torch.from_numpy(t0.reshape(-1)))
+        K = self.BEAM_POLL
+
+        def body(i0):
+            for i in range(i0, min(i0 + K, npos)):
+                ses.step(i, toks.data_ptr())
+                ses.argmax_into(hyp_buf.data_ptr())               # (leaves the log-sum-exp of the rows in ses.junk[:B])
+                check(self.lib.mtl_beam_rank(self.stream, ses.logits.data_ptr(), ses.junk.data_ptr(), state.data_ptr(), toks.data_ptr(),
+                                             parent.data_ptr(), i, T4, Uc, W, V, npos, eos_id), 'mtl_beam_rank')
+                if i + 1 < npos:
+                    ses.gather(tables, parent.data_ptr(), i + 1)
+        # every address of a block of K positions is fixed: eager at its first sighting, recorded at the second, replayed afterwards
+        key = ('beamb', theta.data_ptr(), Uc, W, T4, steps, start_token, eos_id, toks.data_ptr(), state.data_ptr(), self.stream, ses.fast)
+        store = self.__dict__.setdefault('_beamb_lists', {})
+        ent = store.get(key)
+        if ent is None or ent['epoch'] != self.scratch_epoch:
+            while len(store) >= 4:
+                store.pop(next(iter(store)))
+            ent = store[key] = dict(epoch=self.scratch_epoch, seen=set(), lists={})
+        pin = self.__dict__.get('_beamb_pin')
+        if pin is None or pin.numel() < 4 * Uc:
+            pin = self._beamb_pin = torch.empty(4 * max(Uc, 16), dtype=torch.int32).pin_memory()
+        for i0 in range(0, npos, K):
+            cl = ent['lists'].get(i0)
+            if self.prof is not None or isinstance(self.lib, _lib.Recorder) or ent['epoch'] != self.scratch_epoch:
+                body(i0)
+            elif cl is not None:
+                cl.run()
+            elif i0 in ent['seen']:
+                cl, real = _lib.CommandList(), self.lib
+                self.lib = _lib.Recorder(real, cl)
+                try:
+                    body(i0)
+                finally:
+                    self.lib = real
+                if ent['epoch'] == self.scratch_epoch:
+                    ent['lists'][i0] = cl.finish()
+            else:
+                ent['seen'].add(i0)
+                body(i0)
+            if i0 + K < npos:
+                pin[:4 * Uc].copy_(state[:4 * Uc], non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+                if bool((pin[:4 * Uc].view(Uc, 4)[:, 1] != 0).all()):
+                    break
+        host = state.cpu().numpy()                                # (synchronises: the one read-back of the chunk)
+        return beam_unpack(host, Uc, W, npos, start_token, eos_id)
 
     def backward(self, grad, scale=1.0, dpred=None, sG=0):
         """Accumulate `scale` * dLoss/dtheta of the LAST forward into the flat buffer `grad` (+=).

@@ -40,6 +40,12 @@ def post_process(string, special_token_list):
     return string.replace('▁', ' ')
 
 
+def compute_num_params(model):
+    """utils/functions.py:36-41 -> (trainable, non-trainable) parameter counts"""
+    sizes = [(int(p.numel()), int(p.requires_grad)) for p in model.parameters()]
+    return sum(n * t for n, t in sizes), sum(n * (1 - t) for n, t in sizes)
+
+
 def _as_torch_opt(opt):
     return opt.to_torch() if hasattr(opt, 'to_torch') else opt
 

@@ -1,8 +1,11 @@
-"""Loss / CER helpers with the reference's call signatures (utils/metrics.py:38-126), backed by the HIP cross-entropy kernels
+"""Loss / CER / WER helpers with the reference's call signatures (utils/metrics.py:7-126), backed by the HIP cross-entropy kernels
 and the C Levenshtein helper."""
+import ctypes
+
 import torch
 
 from . import _lib
+from .data import get_word_segments_per_language, is_contain_chinese_word
 
 check = _lib.check
 
@@ -10,6 +13,39 @@ check = _lib.check
 def calculate_cer(s1, s2):
     """utils/metrics.py:38-44 (python-Levenshtein replaced by mtl_levenshtein_u32)."""
     return _lib.levenshtein(s1, s2)
+
+
+def calculate_wer(s1, s2):
+    """utils/metrics.py:48-66: edit distance between the two sentences' word sequences (str.split()).  The words are numbered and
+    the id sequences go to mtl_levenshtein_u32 as they are (the reference maps the ids to characters with chr() only because its
+    Levenshtein package takes strings)."""
+    w1, w2 = s1.split(), s2.split()
+    ids = {}
+    for w in w1 + w2:
+        ids.setdefault(w, len(ids))
+    arr = lambda ws: (ctypes.c_uint * max(len(ws), 1))(*[ids[w] for w in ws])
+    a, b = arr(w1), arr(w2)
+    d = _lib.lib().mtl_levenshtein_u32(ctypes.cast(a, ctypes.c_void_p), len(w1), ctypes.cast(b, ctypes.c_void_p), len(w2))
+    if d < 0:
+        raise RuntimeError('mtl_levenshtein_u32 failed: %d' % d)
+    return d
+
+
+def calculate_cer_en_zh(s1, s2):
+    """utils/metrics.py:7-36: (hyp, gold) -> (English edit distance, Chinese edit distance, English gold characters, Chinese gold
+    characters).  Both sentences are cut into word segments per language (get_word_segments_per_language); the segments holding a
+    Chinese character are concatenated into the Chinese sequence, the others into the English one."""
+    seqs = []
+    for s in (s1, s2):
+        en, zh = '', ''
+        for segment in get_word_segments_per_language(s):
+            if is_contain_chinese_word(segment):
+                zh += segment
+            else:
+                en += segment
+        seqs.append((en, zh))
+    (en1, zh1), (en2, zh2) = seqs
+    return calculate_cer(en1, en2), calculate_cer(zh1, zh2), len(en2), len(zh2)
 
 
 class _CrossEntropyFn(torch.autograd.Function):

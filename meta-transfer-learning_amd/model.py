@@ -309,7 +309,7 @@ class Transformer(nn.Module):
             raise RuntimeError('copy_grad accumulation needs the HIP library on an MI355X device')
 
     def evaluate(self, padded_input, input_lengths, padded_target, args=None, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
-                 lm_rescoring=False, lm_weight=0.1, c_weight=1, start_token=-1, verbose=False, max_steps=300):
+                 lm_rescoring=False, lm_weight=0.1, c_weight=1, start_token=-1, verbose=False, max_steps=300, device_ranking=False):
         """models/asr/transformer.py:162-202: returns (None, strs_hyps, strs_gold).
         The encoder + teacher-forced decoder pass supplies the gold strings exactly like the reference.  Greedy hypotheses come
         from PassEngine.greedy_decode (K/V-cached, device-resident token feedback); beam_search=True runs
@@ -317,7 +317,9 @@ class Transformer(nn.Module):
         (all n-best strings of all utterances, concatenated; falls back to greedy when the best hypothesis is empty).
         lm_rescoring=True with beam_search=True (modules/decoder.py:248-256): every ended hypothesis of the batch is scored by the
         word-level LM `lm` (lmscore.LM) in ONE device pass after the search, final_score = score + lm_weight * (lm_score - 2 oov) +
-        sqrt(LM words + 1) * c_weight, and each utterance's hypotheses are re-sorted (stable) by it; ignored by the greedy search."""
+        sqrt(LM words + 1) * c_weight, and each utterance's hypotheses are re-sorted (stable) by it; ignored by the greedy search.
+        device_ranking=True with beam_search=True: the utterances of the batch go through PassEngine.beam_decode_batch (hypotheses
+        ranked on the device, several utterances per decoder step) instead of one beam_decode each; same hypotheses, same scores."""
         if lm_rescoring and beam_search and lm is None:
             raise ValueError('lm_rescoring=True needs lm= (an lmscore.LM)')
         rescoring = bool(lm_rescoring and beam_search)
@@ -339,12 +341,19 @@ class Transformer(nn.Module):
             if beam_search:
                 mem = mem.clone()                                              # the decode buffers live in the same arena
                 ids_nbest, ended = [], []
-                for b in range(B):
-                    ended.append([] if rescoring else None)
-                    res = eng.beam_decode(self._theta, mem.data_ptr() + 4 * b * T4 * eng.hp.d, T4, start, args.beam_width,
-                                          args.beam_nbest, args.tgt_max_len, self._num_words, self.vocab.EOS_ID, c_weight,
-                                          ended_out=ended[b])
-                    if not rescoring:
+                if device_ranking:
+                    ended = [[] for _ in range(B)] if rescoring else None
+                    per_utt = eng.beam_decode_batch(self._theta, mem.data_ptr(), B, T4, start, args.beam_width, args.beam_nbest,
+                                                    args.tgt_max_len, self._num_words, self.vocab.EOS_ID, c_weight, ended_out=ended)
+                else:
+                    per_utt = []
+                    for b in range(B):
+                        ended.append([] if rescoring else None)
+                        per_utt.append(eng.beam_decode(self._theta, mem.data_ptr() + 4 * b * T4 * eng.hp.d, T4, start, args.beam_width,
+                                                       args.beam_nbest, args.tgt_max_len, self._num_words, self.vocab.EOS_ID, c_weight,
+                                                       ended_out=ended[b]))
+                if not rescoring:
+                    for res in per_utt:
                         ids_nbest.extend(yseq for yseq, _score in res)
                 if rescoring:
                     from .lmscore import rescore
