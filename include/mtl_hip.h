@@ -395,6 +395,21 @@ int mtl_sumsq(void* stream, const float* x, long n, float* out, float* workspace
  * out[f*T + t] = log1p(|X[t][f]|), optionally followed by (x - mean) / std (unbiased) over the whole utterance.
  * partials: >= 256 doubles of scratch. */
 int mtl_spect_logmag(void* stream, const float* reim, int ld, int T, int F, float* out, double* partials, int normalize);
+/* The whole front-end for a sampled batch of K utterances in two launches (csrc/mtl_spect.hip; utils/data_loader.py:65-96 per utterance,
+ * and the zero-padded (K, 1, F, Tmax) batch of :284-297): framing, STFT, |.|, log1p, per-utterance (x - mean) / std and the padding.
+ *   wav: the K waveforms concatenated; offsets: K + 1 int64, utterance k = wav[offsets[k] .. offsets[k+1]), L_k samples, T_k = 1 + L_k / hop
+ *   frames.  Sample n of frame t is index t hop + n - n_fft/2 of the utterance, reflected once at either end (center=True,
+ *   pad_mode='reflect'): L_k >= n_fft/2 + 1 is the CALLER's promise (the offsets live on the device; the kernel clamps, it cannot refuse).
+ *   basis: n_fft x ldb, [w cos | -w sin] (F columns each), ldb >= 2 F.  n_fft even and <= 1024, hop >= 1, F = n_fft/2 + 1, 1 <= K <= 2^20, Tmax >= 1.
+ *   out (K, F, Tmax): out[k][f][t] = log1p|X_k[t][f]| for t < min(T_k, Tmax), normalised when `normalize` with the mean / unbiased std over
+ *   ALL F T_k values of the utterance (frames beyond Tmax count), and exactly 0 for min(T_k, Tmax) <= t < Tmax.
+ * The frames are formed inside the kernel from an LDS-staged span of samples (no padded copy, no frame matrix in memory), the product
+ * runs on v_mfma_f32_16x16x4_f32, the statistics are fp64 partials combined in a fixed order: bitwise repeatable, no atomics.  The
+ * number of launches (2) and the grid do not depend on the lengths.  workspace: mtl_spect_batch_workspace(sum of T_k, K, F) bytes,
+ * 8-byte aligned. */
+long mtl_spect_batch_workspace(long total_frames, int K, int F);
+int mtl_spect_batch(void* stream, const float* wav, const long* offsets, int K, int n_fft, int hop, const float* basis, int ldb, int F,
+                    float* out, int Tmax, int normalize, void* workspace, long workspace_bytes);
 
 /* ---- LSTM cell, one time step (lm/model/rnn_model.py:20 nn.LSTM; lm/main_meta_transfer.py:277-411) ----------
  * gx = x_t . W_ih^T + b_ih and gh = h_{t-1} . W_hh^T + b_hh come from mtl_gemm_f32_ex (B x 4H each, torch gate order i|f|g|o).

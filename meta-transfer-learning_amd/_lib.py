@@ -111,6 +111,8 @@ SIGNATURES = {
     'mtl_adam_step': (I, [P, P, P, P, P, I, F, F, F, F, L]),
     'mtl_sumsq': (I, [P, P, L, P, P, I, F]),
     'mtl_spect_logmag': (I, [P, P, I, I, I, P, P, I]),
+    'mtl_spect_batch_workspace': (L, [L, I, I]),
+    'mtl_spect_batch': (I, [P, P, P, I, I, I, P, I, I, P, I, I, P, L]),
     'mtl_lstm_cell_fwd': (I, [P, P, P, P, P, P, P, P, P, F, I, I]),
     'mtl_lstm_cell_bwd': (I, [P, P, P, F, P, P, P, P, P, P, P, I, I]),
     'mtl_lstm_layer_supported': (I, [I, I]),

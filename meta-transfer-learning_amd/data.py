@@ -135,8 +135,20 @@ class ManifestTaskDataset:
     see the same draws (tasks are sharded AFTER sampling, the validation batch is shared), so pass the same seed on all ranks.
     `__getitem__` / `__len__` follow utils/data_loader.py:323-340 (validation / test use: manifest 0 only unless is_train)."""
 
-    def __init__(self, vocab, args, manifest_filepath_list, feature_fn=None, partitions=None, seed=None, is_train=False):
-        if feature_fn is None:
+    def __init__(self, vocab, args, manifest_filepath_list, feature_fn=None, partitions=None, seed=None, is_train=False,
+                 device_batches=False):
+        """device_batches=True: `sample()` featurises each part (train / validation) with ONE `SpectrogramFrontEnd.batch` call and
+        returns `inputs` on the device (the trainers copy device-resident inputs straight into their static buffers); the sizes,
+        percentages and targets stay host tensors as `collate` makes them, and the index stream is the same.  The front-end is
+        built at the first `sample()`, so constructing the dataset needs no device.  `__getitem__` keeps the per-utterance path."""
+        if device_batches and feature_fn is not None:
+            raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
+        self.device_batches, self._fe = device_batches, None
+        self._fe_factory = lambda: SpectrogramFrontEnd(args.sample_rate, args.window_size, args.window_stride,
+                                                       getattr(args, 'window', 'hamming'), True)
+        if device_batches:
+            feature_fn = lambda path: self._front_end()(load_wav_pcm16(path)).cpu()
+        elif feature_fn is None:
             # default: 16-bit PCM wav -> device spectrogram front-end (SpectrogramParser.parse_audio, normalize=True as in
             # meta_transfer_train.py:161), handed back on the host like the reference's parse_audio output
             fe = SpectrogramFrontEnd(args.sample_rate, args.window_size, args.window_stride, getattr(args, 'window', 'hamming'), True)
@@ -166,6 +178,26 @@ class ManifestTaskDataset:
             trans.append(parse_transcript(self.vocab, txt))
         return spects, trans
 
+    def _front_end(self):
+        if self._fe is None:
+            self._fe = self._fe_factory()
+        return self._fe
+
+    def _device_part(self, ids, picks):
+        """one part of a sampled batch through SpectrogramFrontEnd.batch: the 5-tuple of `collate` with `inputs` on the device"""
+        waves = [load_wav_pcm16(ids[j][0]) for j in picks]
+        trans = [parse_transcript(self.vocab, ids[j][1]) for j in picks]
+        inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len)
+        k, max_t = len(trans), inputs.size(3)
+        input_percentages = torch.zeros(k, dtype=torch.float32)
+        targets = torch.full((k, max(len(t) for t in trans)), self.vocab.PAD_ID, dtype=torch.int64)
+        target_sizes = torch.zeros(k, dtype=torch.int32)
+        for i, t in enumerate(trans):
+            input_percentages[i] = int(input_sizes[i]) / float(max_t)
+            targets[i, :len(t)] = torch.tensor(t, dtype=torch.int64)
+            target_sizes[i] = len(t)
+        return inputs, input_sizes, input_percentages, targets, target_sizes
+
     def sample(self, k_train, k_val, manifest_id, need=(True, True)):
         """utils/data_loader.py:245-321.  need = (train part, validation part): a part that the caller will not use is still DRAWN
         (the index stream stays what the reference's is, and identical on every rank) but not loaded / featurised / collated --
@@ -173,6 +205,10 @@ class ManifestTaskDataset:
         several ranks, only its own tasks' training batches."""
         ids = self.ids_list[manifest_id]
         picks = self.rng.choice(np.arange(0, len(ids)), k_train + k_val, p=self.proba[manifest_id], replace=True)
+        if self.device_batches:
+            tr = self._device_part(ids, picks[:k_train]) if need[0] else None
+            va = self._device_part(ids, picks[k_train:k_train + k_val]) if need[1] else None
+            return tr, va
         tr = collate(*self._rows(ids, picks[:k_train]), pad_id=self.vocab.PAD_ID) if need[0] else None
         va = collate(*self._rows(ids, picks[k_train:k_train + k_val]), pad_id=self.vocab.PAD_ID) if need[1] else None
         return tr, va
@@ -202,10 +238,12 @@ class SpectrogramDataset(ManifestTaskDataset):
     attributes as the reference object (max_size, ids_list, proba, part_len, input_type, manifest_filepath_list, is_train) and the
     same two console lines.  Outside the accelerated path and rejected loudly: augment=True (sox tempo / gain perturbation),
     noise injection (audio_conf['noise_dir']), input_type other than 'char' (the bpe / ipa branches are commented out in the
-    reference too)."""
+    reference too).  device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off)."""
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
-                 is_train=False, partitions=None, feature_fn=None, seed=None):
+                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False):
+        if device_batches and feature_fn is not None:
+            raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
         if augment:
             raise NotImplementedError('augment=True (sox tempo / gain perturbation, utils/data_loader.py:28-38) is outside the accelerated path')
         if audio_conf.get('noise_dir') is not None:
@@ -215,16 +253,19 @@ class SpectrogramDataset(ManifestTaskDataset):
         self.window_stride, self.window_size = audio_conf['window_stride'], audio_conf['window_size']
         self.sample_rate, self.window = audio_conf['sample_rate'], audio_conf.get('window', 'hamming')
         self.normalize, self.augment, self.noise_prob = normalize, augment, audio_conf.get('noise_prob')
-        if feature_fn is None:
-            fe = []       # built at the first utterance: constructing the dataset must not need the device
+        fe = []           # built at the first utterance: constructing the dataset must not need the device
 
+        def front_end():
+            if not fe:
+                fe.append(SpectrogramFrontEnd(self.sample_rate, self.window_size, self.window_stride,
+                                              self.window if self.window in ('hamming', 'hann', 'blackman', 'bartlett') else 'hamming',
+                                              self.normalize))
+            return fe[0]
+        if feature_fn is None:
             def feature_fn(path):
-                if not fe:
-                    fe.append(SpectrogramFrontEnd(self.sample_rate, self.window_size, self.window_stride,
-                                                  self.window if self.window in ('hamming', 'hann', 'blackman', 'bartlett') else 'hamming',
-                                                  self.normalize))
-                return fe[0](load_wav_pcm16(path)).cpu()
+                return front_end()(load_wav_pcm16(path)).cpu()
         super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
+        self.device_batches, self._fe_factory = device_batches, front_end       # (sample() of a part: one front_end().batch call)
         self.manifest_filepath_list, self.input_type = manifest_filepath_list, input_type
         # (the reference leaves part_len at the LAST manifest's partition size, or max_size without partitions: :211-222)
         self.part_len = (max(int(len(self.ids_list[-1]) * partitions[len(self.ids_list) - 1]), 1) if partitions is not None
@@ -330,12 +371,40 @@ def load_wav_pcm16(path):
     return raw.reshape(-1, ch).mean(axis=1).astype(np.float32) if ch > 1 else raw
 
 
+def pack_waveforms(waves, hop, n_fft, max_frames=None):
+    """K one-dimensional waveforms -> (flat float32 (sum of L_k), offsets int64 (K + 1), frames int32 (K), Tmax): the host side of
+    `SpectrogramFrontEnd.batch`, pure numpy.  frames[k] = min(1 + L_k // hop, max_frames), Tmax = max(frames).  An utterance shorter
+    than n_fft // 2 + 1 samples would need more than one reflection at its ends (numpy reflects repeatedly there): rejected."""
+    if len(waves) == 0:
+        raise ValueError('pack_waveforms: an empty list of waveforms')
+    arrs = []
+    for i, w in enumerate(waves):
+        a = np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError('pack_waveforms: waveform %d is not one-dimensional (shape %s)' % (i, a.shape))
+        if a.shape[0] < n_fft // 2 + 1:
+            raise ValueError('pack_waveforms: utterance %d has %d samples, fewer than n_fft // 2 + 1 = %d (one reflection must suffice)'
+                             % (i, a.shape[0], n_fft // 2 + 1))
+        arrs.append(a)
+    lengths = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+    offsets = np.zeros(len(arrs) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    frames = 1 + lengths // hop
+    if max_frames is not None:
+        frames = np.minimum(frames, max_frames)
+    frames = frames.astype(np.int32)
+    return np.concatenate(arrs), offsets, frames, int(frames.max())
+
+
 class SpectrogramFrontEnd:
     """wav -> STFT (n_fft = win = sample_rate*window_size, hop = sample_rate*window_stride, symmetric Hamming window,
     center + reflect padding = librosa.stft defaults of the reference era) -> |.| -> log1p -> (x-mean)/std, all on the MI355X:
     the STFT is one fp32-MFMA GEMM (frames = overlapping rows of the padded waveform, lda = hop) against a windowed DFT basis."""
 
-    def __init__(self, sample_rate=16000, window_size=0.02, window_stride=0.01, window='hamming', normalize=True, device='cuda'):
+    def __init__(self, sample_rate=16000, window_size=0.02, window_stride=0.01, window='hamming', normalize=True, device='cuda',
+                 consumer=None):
+        """consumer: the stream on which the batches of `batch()` are read (default: the device's current stream at construction --
+        the stream on which TransientTrainer._batched_iteration copies device-resident inputs into its static buffers)."""
         from scipy.signal import windows as sw
         self.n_fft = int(sample_rate * window_size)
         self.hop = int(sample_rate * window_stride)
@@ -353,6 +422,9 @@ class SpectrogramFrontEnd:
         basis[:, self.F:2 * self.F] = (-win[:, None] * np.sin(ang)).astype(np.float32)
         self.basis = torch.from_numpy(basis).to(self.device)
         self.partials = torch.empty(512, dtype=torch.float64, device=self.device)
+        self.consumer = consumer if consumer is not None or self.device.type != 'cuda' else torch.cuda.current_stream(self.device)
+        self.stream = None                                     # batch()'s own stream, made at its first call
+        self._pin_wav = self._pin_off = None                   # pinned staging of batch(), grown on demand
 
     def __call__(self, y):
         """y: 1-D float waveform (numpy or tensor) -> (F, T) fp32 tensor on the device, T = 1 + len(y) // hop."""
@@ -372,3 +444,51 @@ class SpectrogramFrontEnd:
         _lib.check(lib.mtl_spect_logmag(st, reim.data_ptr(), self.ldb, T, self.F, out.data_ptr(), self.partials.data_ptr(),
                                         1 if self.normalize else 0), 'mtl_spect_logmag')
         return out
+
+    def batch(self, waves, max_frames=None):
+        """K waveforms -> (inputs (K, 1, F, Tmax) fp32 on the device, input_sizes (K) int32 on the host): what `collate` builds from
+        K `__call__` results cut to max_frames, in one device pass -- one pinned staging copy of the concatenated samples and of the
+        offsets (two H2D copies) and the two launches of mtl_spect_batch (framing, STFT, log-magnitude, per-utterance statistics over
+        the WHOLE utterance, normalisation, zero padding).
+
+        Streams and lifetime: the front-end owns one stream.  `inputs` is allocated with that stream current (its block belongs to
+        that stream's pool), the copies and launches run there, and the calling thread waits on an event recorded behind them: the
+        batch is complete when this returns, whatever the training kernels queued on other streams are doing, and nothing here
+        waits for them (no device-wide synchronisation).  `inputs.record_stream(consumer)` then tells the allocator that `consumer`
+        reads the block: the trainer's host thread enqueues up to two iterations ahead, so the tensor is usually dropped while the
+        trainer's copy of it is still pending -- without the record the next `batch` call could be handed the same memory and
+        overwrite it under that copy."""
+        from . import _lib
+        if self.device.type != 'cuda':
+            raise RuntimeError('the spectrogram front-end runs on the MI355X only (no CPU fallback)')
+        lib = _lib.lib()
+        flat, offsets, frames, tmax = pack_waveforms(waves, self.hop, self.n_fft, max_frames)
+        K = len(frames)
+        total_frames = int((1 + np.diff(offsets) // self.hop).sum())
+        ws_bytes = lib.mtl_spect_batch_workspace(total_frames, K, self.F)
+        if ws_bytes < 0:
+            raise RuntimeError('mtl_spect_batch_workspace failed with code %d' % ws_bytes)
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(self.device)
+        if self._pin_wav is None or self._pin_wav.numel() < flat.shape[0]:
+            self._pin_wav = torch.empty(max(flat.shape[0], 1 << 16), dtype=torch.float32).pin_memory()
+        if self._pin_off is None or self._pin_off.numel() < K + 1:
+            self._pin_off = torch.empty(max(K + 1, 64), dtype=torch.int64).pin_memory()
+        # the staging buffers are free again: every earlier call waited for its copies before it returned
+        self._pin_wav[:flat.shape[0]].copy_(torch.from_numpy(flat))
+        self._pin_off[:K + 1].copy_(torch.from_numpy(offsets))
+        with torch.cuda.stream(self.stream):
+            inputs = torch.empty(K, 1, self.F, tmax, device=self.device)
+            d_wav = torch.empty(flat.shape[0], device=self.device)
+            d_off = torch.empty(K + 1, dtype=torch.int64, device=self.device)
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+            d_wav.copy_(self._pin_wav[:flat.shape[0]], non_blocking=True)
+            d_off.copy_(self._pin_off[:K + 1], non_blocking=True)
+            _lib.check(lib.mtl_spect_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
+                                           self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax, 1 if self.normalize else 0,
+                                           ws.data_ptr(), ws_bytes), 'mtl_spect_batch')
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        done.synchronize()                                     # host wait on this stream's event only
+        inputs.record_stream(self.consumer)
+        return inputs, torch.from_numpy(frames)
