@@ -410,6 +410,27 @@ int mtl_spect_logmag(void* stream, const float* reim, int ld, int T, int F, floa
 long mtl_spect_batch_workspace(long total_frames, int K, int F);
 int mtl_spect_batch(void* stream, const float* wav, const long* offsets, int K, int n_fft, int hop, const float* basis, int ldb, int F,
                     float* out, int Tmax, int normalize, void* workspace, long workspace_bytes);
+/* Noise injection on the device (NoiseInjection.inject_noise_sample, utils/data_loader.py:383-399: data += level * noise *
+ * rms(data) / rms(noise), noise = a segment of a noise file as long as the utterance).  The noise corpus is ONE int16 bank of bank_len
+ * samples resident on the device; utterance k (wav / offsets as in mtl_spect_batch, n = L_k samples) takes bank[noise_off[k] .. + n),
+ * noise_off[k] < 0 = clean.  Every bank address is clamped into [0, bank_len): a wrong table cannot read out of bounds.
+ *   mtl_wave_mix_coef (utils/data_loader.py:383-399, the two energies of :396-397): coef[k] = (float)(level[k] sqrt(S_d / n) /
+ *     sqrt(S_n / n)) formed in fp64, S_d = sum data^2, S_n = sum noise^2 with noise = (float)int16 / 32768 (exact), fp64 partial sums
+ *     combined in a fixed order (no atomics: bitwise repeatable); coef[k] = 0 for noise_off[k] < 0 and for S_n == 0.
+ *     workspace: mtl_wave_mix_coef_workspace(K) bytes, 8-byte aligned. */
+long mtl_wave_mix_coef_workspace(int K);
+int mtl_wave_mix_coef(void* stream, const float* wav, const long* offsets, int K, const short* bank, long bank_len, const long* noise_off,
+                      const float* level, float* coef, void* workspace, long workspace_bytes);
+/*   mtl_wave_mix (utils/data_loader.py:383-399, the sum of :398): out[offsets[k] + i] = fmaf(coef[k], noise_i, wav[offsets[k] + i]) in
+ *     fp32 for the K packed waveforms (out has the layout of wav); coef[k] == 0 or noise_off[k] < 0 copies the utterance bit for bit. */
+int mtl_wave_mix(void* stream, const float* wav, const long* offsets, int K, const short* bank, long bank_len, const long* noise_off,
+                 const float* coef, float* out);
+/*   mtl_spect_batch_noise (utils/data_loader.py:383-399 in front of :65-96): mtl_spect_batch of the MIXED waveforms without forming them
+ *     in memory -- the same kernel, the staged sample being the expression of mtl_wave_mix at the (reflected) index, so the result is
+ *     bitwise that of mtl_spect_batch on mtl_wave_mix's output.  A workgroup of an utterance with coef 0 does not read the bank. */
+int mtl_spect_batch_noise(void* stream, const float* wav, const long* offsets, int K, int n_fft, int hop, const float* basis, int ldb, int F,
+                          float* out, int Tmax, int normalize, void* workspace, long workspace_bytes, const short* bank, long bank_len,
+                          const long* noise_off, const float* coef);
 
 /* ---- LSTM cell, one time step (lm/model/rnn_model.py:20 nn.LSTM; lm/main_meta_transfer.py:277-411) ----------
  * gx = x_t . W_ih^T + b_ih and gh = h_{t-1} . W_hh^T + b_hh come from mtl_gemm_f32_ex (B x 4H each, torch gate order i|f|g|o).

@@ -113,6 +113,10 @@ SIGNATURES = {
     'mtl_spect_logmag': (I, [P, P, I, I, I, P, P, I]),
     'mtl_spect_batch_workspace': (L, [L, I, I]),
     'mtl_spect_batch': (I, [P, P, P, I, I, I, P, I, I, P, I, I, P, L]),
+    'mtl_wave_mix_coef_workspace': (L, [I]),
+    'mtl_wave_mix_coef': (I, [P, P, P, I, P, L, P, P, P, P, L]),
+    'mtl_wave_mix': (I, [P, P, P, I, P, L, P, P, P]),
+    'mtl_spect_batch_noise': (I, [P, P, P, I, I, I, P, I, I, P, I, I, P, L, P, L, P, P]),
     'mtl_lstm_cell_fwd': (I, [P, P, P, P, P, P, P, P, P, F, I, I]),
     'mtl_lstm_cell_bwd': (I, [P, P, P, F, P, P, P, P, P, P, P, I, I]),
     'mtl_lstm_layer_supported': (I, [I, I]),

@@ -18,6 +18,16 @@
 //   launch 2 (spect_finalize_kernel): per utterance the partials summed in index order (fp64), mean / unbiased std as
 //            spect_normalize_kernel (mtl_elem.hip) forms them, rows normalised in place, frames [min(T_k, Tmax), Tmax) zeroed.
 // No atomics: bitwise repeatable.
+//
+// Noise injection (NoiseInjection.inject_noise_sample, utils/data_loader.py:383-399) rides on the staging loop: the noise corpus is one
+// int16 bank resident in HBM, utterance k takes the n = L_k samples from bank[noise_off[k]] on (noise_off[k] < 0: clean), and
+//   mtl_wave_mix_coef     coef[k] = level[k] sqrt(S_d / n) / sqrt(S_n / n), S_d / S_n the fp64 sums of squares of the utterance and of its
+//                         noise segment: MIX_SLOTS workgroups per utterance over contiguous chunks, one fp64 partial pair each (threads
+//                         stride their chunk, lanes are combined by shuffles, the four waves in index order), then one thread per
+//                         utterance adds the partials in slot order.  coef = 0 for a clean utterance and for S_n = 0.
+//   mtl_wave_mix          out = mix(coef[k], bank, wav): the unfused form
+//   spect_batch_kernel<G, true>   stages mix(...) instead of wav: the reflect index j addresses the MIXED signal, so both reads use it
+// `mix` is ONE expression (sp_mix below) in every kernel, so the fused and the unfused path agree bit for bit.
 #include "mtl_common.h"
 
 namespace {
@@ -28,6 +38,10 @@ constexpr int SP_SLOTS = 32;          // workgroups (partials) per utterance and
 constexpr int SP_FB = 64;             // frequencies per workgroup: 4 waves x 16
 constexpr int SP_CAP = 24576;         // floats of LDS for the padded span (96 KB): 16 frames of n_fft = 1024 at any hop fit
 constexpr int SP_HEAD = 16;           // floats in front of the span: the cross-wave reduction scratch (8 doubles)
+#ifndef MTL_MIX_SLOTS
+#define MTL_MIX_SLOTS 32              // workgroups per utterance of the energy pass (1: one workgroup forms the coefficient itself, one launch)
+#endif
+constexpr int MIX_SLOTS = MTL_MIX_SLOTS;
 
 // one pad word per 32: a frame stride that is a multiple of 32 words (hop = 160) would put the 16 frames of a B fragment on one bank
 __device__ __forceinline__ int sp_pad(int q) { return q + (q >> 5); }
@@ -41,9 +55,24 @@ struct SpectP {
     int K, n_fft, hop, ldb, F, Tmax, nfb;
     int fs;          // LDS distance of two consecutive frames: min(hop, n_fft) (frames are packed when they do not overlap)
     int span;        // staged floats: (16 G - 1) fs + n_fft + 16 (the last 16 are zeros: the K loop runs in trips of 16 samples)
+    // noise injection (spect_batch_kernel<G, true> only)
+    const short* bank;
+    const long* noise_off;
+    const float* coef;
+    long bank_len;
 };
 
-template <int G>
+// sample i of an utterance mixed with sample i of its noise segment (utils/data_loader.py:398): fmaf(c, noise, data) in fp32 with
+// noise = (float)int16 / 32768 (exact).  The bank address is clamped into [0, bank_len): a wrong table cannot read out of bounds.
+// c == 0 (clean utterance, level 0, silent segment) never touches the bank and returns the sample itself, signed zeros included.
+__device__ __forceinline__ float sp_mix(float c, const short* __restrict__ bank, long bank_len, long noff, long i, float x) {
+    if (c == 0.f) return x;
+    long b = noff + i;
+    b = b < 0 ? 0 : (b >= bank_len ? bank_len - 1 : b);
+    return fmaf(c, (float)bank[b] * (1.f / 32768.f), x);
+}
+
+template <int G, bool NOISE>
 __global__ __launch_bounds__(256) void spect_batch_kernel(const SpectP p) {
     extern __shared__ __attribute__((aligned(16))) float sp_lds[];
     double* red = reinterpret_cast<double*>(sp_lds);
@@ -69,6 +98,12 @@ __global__ __launch_bounds__(256) void spect_batch_kernel(const SpectP p) {
     const float* bim = bre + p.F;
     const int nsteps = (p.n_fft + 3) >> 2;
     double s = 0.0, q2 = 0.0;
+    float ck = 0.f;                                                       // uniform over the workgroup: 0 leaves the bank untouched
+    long noff = 0;
+    if constexpr (NOISE) {
+        noff = p.noise_off[k];
+        ck = noff < 0 ? 0.f : p.coef[k];
+    }
 
     for (int tile = slot; tile < ntiles; tile += SP_SLOTS) {
         const int t0 = tile * TF;
@@ -93,7 +128,8 @@ __global__ __launch_bounds__(256) void spect_batch_kernel(const SpectP p) {
                 if (j < 0) j = -j;                                        // center=True, pad_mode='reflect'
                 if (j >= L) j = 2 * (L - 1) - j;
                 j = j < 0 ? 0 : (j >= L ? L - 1 : j);                     // a no-op for q < live when L >= n_fft / 2 + 1; never out of bounds
-                const float x = p.wav[off + j];
+                float x = p.wav[off + j];
+                if constexpr (NOISE) x = sp_mix(ck, p.bank, p.bank_len, noff, j, x);
                 v[u] = q < live ? x : 0.f;
             }
 #pragma unroll
@@ -214,14 +250,126 @@ __global__ __launch_bounds__(256) void spect_finalize_kernel(float* __restrict__
     for (int t = Tst + (threadIdx.x & 63); t < Tmax; t += 64) row[t] = 0.f;
 }
 
+// energy pass: grid K * MIX_SLOTS, workgroup (k, slot) sums the squares of chunk `slot` of utterance k and of its noise segment
+__global__ __launch_bounds__(256) void wave_mix_energy_kernel(const float* __restrict__ wav, const long* __restrict__ offsets, int K,
+                                                              const short* __restrict__ bank, long bank_len,
+                                                              const long* __restrict__ noise_off, const float* __restrict__ level,
+                                                              double* __restrict__ part, float* __restrict__ coef) {
+    __shared__ double red[8];
+    const int k = blockIdx.x % K, slot = blockIdx.x / K;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long off = offsets[k];
+    const long L = offsets[k + 1] - off;
+    const long noff = noise_off[k];
+    const long chunk = ((L + MIX_SLOTS - 1) / MIX_SLOTS + 255) / 256 * 256;
+    const long i0 = slot * chunk, i1 = i0 + chunk < L ? i0 + chunk : L;
+    double sd = 0.0, sn = 0.0;
+    if (noff >= 0) {
+        for (long b = i0 + tid; b < i1; b += 8 * 256) {
+            float d[8], n[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {                                 // eight loads of either kind in flight, from clamped addresses
+                long i = b + 256 * u;
+                const bool on = i < i1;
+                i = on ? i : i1 - 1;
+                long a = noff + i;
+                a = a >= bank_len ? bank_len - 1 : a;
+                d[u] = on ? wav[off + i] : 0.f;
+                n[u] = on ? (float)bank[a] * (1.f / 32768.f) : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                sd = fma((double)d[u], (double)d[u], sd);
+                sn = fma((double)n[u], (double)n[u], sn);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sd += __shfl_xor(sd, o, 64);
+        sn += __shfl_xor(sn, o, 64);
+    }
+    if (lane == 0) {
+        red[2 * wave] = sd;
+        red[2 * wave + 1] = sn;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    sd = (red[0] + red[2]) + (red[4] + red[6]);
+    sn = (red[1] + red[3]) + (red[5] + red[7]);
+    if (MIX_SLOTS > 1) {
+        part[((long)k * MIX_SLOTS + slot) * 2] = sd;
+        part[((long)k * MIX_SLOTS + slot) * 2 + 1] = sn;
+    } else {
+        const double n = (double)L;
+        coef[k] = noff >= 0 && sn > 0.0 ? (float)((double)level[k] * sqrt(sd / n) / sqrt(sn / n)) : 0.f;
+    }
+}
+
+// a thread per utterance: the partials in slot order, the coefficient in fp64, rounded once to fp32
+__global__ __launch_bounds__(64) void wave_mix_coef_kernel(const long* __restrict__ offsets, int K, const long* __restrict__ noise_off,
+                                                           const float* __restrict__ level, const double* __restrict__ part,
+                                                           float* __restrict__ coef) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= K) return;
+    double sd = 0.0, sn = 0.0;
+    for (int i = 0; i < MIX_SLOTS; ++i) {
+        sd += part[((long)k * MIX_SLOTS + i) * 2];
+        sn += part[((long)k * MIX_SLOTS + i) * 2 + 1];
+    }
+    const double n = (double)(offsets[k + 1] - offsets[k]);
+    coef[k] = noise_off[k] >= 0 && sn > 0.0 ? (float)((double)level[k] * sqrt(sd / n) / sqrt(sn / n)) : 0.f;
+}
+
+// grid K * MIX_SLOTS: workgroup (k, slot) writes samples slot 256 + tid, + 256 MIX_SLOTS, ... of utterance k
+__global__ __launch_bounds__(256) void wave_mix_kernel(const float* __restrict__ wav, const long* __restrict__ offsets, int K,
+                                                       const short* __restrict__ bank, long bank_len, const long* __restrict__ noise_off,
+                                                       const float* __restrict__ coef, float* __restrict__ out) {
+    const int k = blockIdx.x % K, slot = blockIdx.x / K;
+    const long off = offsets[k];
+    const long L = offsets[k + 1] - off;
+    const long noff = noise_off[k];
+    const float ck = noff < 0 ? 0.f : coef[k];
+    for (long i = (long)slot * 256 + threadIdx.x; i < L; i += 256L * MIX_SLOTS) out[off + i] = sp_mix(ck, bank, bank_len, noff, i, wav[off + i]);
+}
+
 int sp_nfb(int F) { return (F + SP_FB - 1) / SP_FB; }
 
-template <int G>
+template <int G, bool NOISE>
 int launch_batch(hipStream_t s, const SpectP& p, int lds_bytes) {
-    static int attr = hipFuncSetAttribute(reinterpret_cast<const void*>(spect_batch_kernel<G>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (SP_HEAD + SP_CAP) * 4) == hipSuccess ? 0 : MTL_ELAUNCH;
+    static int attr = hipFuncSetAttribute(reinterpret_cast<const void*>(spect_batch_kernel<G, NOISE>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (SP_HEAD + SP_CAP) * 4) == hipSuccess ? 0 : MTL_ELAUNCH;
     if (attr) return attr;
-    hipLaunchKernelGGL(spect_batch_kernel<G>, dim3(p.K * SP_SLOTS * p.nfb), dim3(256), lds_bytes, s, p);
+    hipLaunchKernelGGL((spect_batch_kernel<G, NOISE>), dim3(p.K * SP_SLOTS * p.nfb), dim3(256), lds_bytes, s, p);
+    return MTL_OK;
+}
+
+// argument checks and the two launches shared by mtl_spect_batch and mtl_spect_batch_noise (p.bank == nullptr: the clean kernel)
+template <bool NOISE>
+int spect_batch(void* stream, SpectP p, int normalize, void* workspace, long workspace_bytes) {
+    if (!p.wav || !p.offsets || !p.basis || !p.out || !workspace) return MTL_EINVAL;
+    if (p.K < 1 || p.K > (1 << 20) || p.n_fft < 2 || p.n_fft > 1024 || (p.n_fft & 1) || p.hop < 1 || p.F != p.n_fft / 2 + 1 ||
+        p.ldb < 2 * p.F || p.Tmax < 1)
+        return MTL_EINVAL;
+    if (workspace_bytes < (long)p.K * SP_SLOTS * sp_nfb(p.F) * 2 * (long)sizeof(double) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return MTL_EINVAL;
+    p.part = static_cast<double*>(workspace);
+    p.nfb = sp_nfb(p.F);
+    p.fs = p.hop < p.n_fft ? p.hop : p.n_fft;
+    hipStream_t s = as_stream(stream);
+    int rc = MTL_EINVAL;
+    for (int G = 4; G >= 1; G >>= 1) {                                   // the widest row tile whose span fits (G = 1 always does)
+        p.span = (16 * G - 1) * p.fs + p.n_fft + 16;
+        const int floats = p.span + (p.span >> 5) + 1;
+        if (floats > SP_CAP) continue;
+        const int lds = (SP_HEAD + floats) * 4;
+        rc = G == 4 ? launch_batch<4, NOISE>(s, p, lds) : G == 2 ? launch_batch<2, NOISE>(s, p, lds) : launch_batch<1, NOISE>(s, p, lds);
+        break;
+    }
+    if (rc != MTL_OK) return rc;
+    hipLaunchKernelGGL(spect_finalize_kernel, dim3(p.K, (p.F + 3) / 4), dim3(256), 0, s, p.out, p.offsets, p.part, p.hop, p.F, p.Tmax, p.nfb,
+                       normalize);
+    MTL_CHECK_LAUNCH();
     return MTL_OK;
 }
 
@@ -236,28 +384,49 @@ long mtl_spect_batch_workspace(long total_frames, int K, int F) {
 
 int mtl_spect_batch(void* stream, const float* wav, const long* offsets, int K, int n_fft, int hop, const float* basis, int ldb, int F,
                     float* out, int Tmax, int normalize, void* workspace, long workspace_bytes) {
-    if (!wav || !offsets || !basis || !out || !workspace) return MTL_EINVAL;
-    if (K < 1 || K > (1 << 20) || n_fft < 2 || n_fft > 1024 || (n_fft & 1) || hop < 1 || F != n_fft / 2 + 1 || ldb < 2 * F || Tmax < 1)
-        return MTL_EINVAL;
-    if (workspace_bytes < mtl_spect_batch_workspace(K, K, F) || (reinterpret_cast<uintptr_t>(workspace) & 7)) return MTL_EINVAL;
-    SpectP p;
-    p.wav = wav, p.offsets = offsets, p.basis = basis, p.out = out, p.part = static_cast<double*>(workspace);
-    p.K = K, p.n_fft = n_fft, p.hop = hop, p.ldb = ldb, p.F = F, p.Tmax = Tmax, p.nfb = sp_nfb(F);
-    p.fs = hop < n_fft ? hop : n_fft;
+    SpectP p = {};
+    p.wav = wav, p.offsets = offsets, p.basis = basis, p.out = out;
+    p.K = K, p.n_fft = n_fft, p.hop = hop, p.ldb = ldb, p.F = F, p.Tmax = Tmax;
+    return spect_batch<false>(stream, p, normalize, workspace, workspace_bytes);
+}
+
+long mtl_wave_mix_coef_workspace(int K) {
+    if (K <= 0 || K > (1 << 20)) return MTL_EINVAL;
+    return (long)K * MIX_SLOTS * 2 * (long)sizeof(double);              // one (S_d, S_n) per (utterance, slot)
+}
+
+int mtl_wave_mix_coef(void* stream, const float* wav, const long* offsets, int K, const short* bank, long bank_len, const long* noise_off,
+                      const float* level, float* coef, void* workspace, long workspace_bytes) {
+    if (!wav || !offsets || !bank || !noise_off || !level || !coef || !workspace) return MTL_EINVAL;
+    if (K < 1 || K > (1 << 20) || bank_len <= 0) return MTL_EINVAL;
+    if (workspace_bytes < mtl_wave_mix_coef_workspace(K) || (reinterpret_cast<uintptr_t>(workspace) & 7)) return MTL_EINVAL;
     hipStream_t s = as_stream(stream);
-    int rc = MTL_EINVAL;
-    for (int G = 4; G >= 1; G >>= 1) {                                   // the widest row tile whose span fits (G = 1 always does)
-        p.span = (16 * G - 1) * p.fs + n_fft + 16;
-        const int floats = p.span + (p.span >> 5) + 1;
-        if (floats > SP_CAP) continue;
-        const int lds = (SP_HEAD + floats) * 4;
-        rc = G == 4 ? launch_batch<4>(s, p, lds) : G == 2 ? launch_batch<2>(s, p, lds) : launch_batch<1>(s, p, lds);
-        break;
-    }
-    if (rc != MTL_OK) return rc;
-    hipLaunchKernelGGL(spect_finalize_kernel, dim3(K, (F + 3) / 4), dim3(256), 0, s, out, offsets, p.part, hop, F, Tmax, p.nfb, normalize);
+    double* part = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(wave_mix_energy_kernel, dim3(K * MIX_SLOTS), dim3(256), 0, s, wav, offsets, K, bank, bank_len, noise_off, level, part, coef);
+    if (MIX_SLOTS > 1)
+        hipLaunchKernelGGL(wave_mix_coef_kernel, dim3((K + 63) / 64), dim3(64), 0, s, offsets, K, noise_off, level, part, coef);
     MTL_CHECK_LAUNCH();
     return MTL_OK;
+}
+
+int mtl_wave_mix(void* stream, const float* wav, const long* offsets, int K, const short* bank, long bank_len, const long* noise_off,
+                 const float* coef, float* out) {
+    if (!wav || !offsets || !bank || !noise_off || !coef || !out) return MTL_EINVAL;
+    if (K < 1 || K > (1 << 20) || bank_len <= 0) return MTL_EINVAL;
+    hipLaunchKernelGGL(wave_mix_kernel, dim3(K * MIX_SLOTS), dim3(256), 0, as_stream(stream), wav, offsets, K, bank, bank_len, noise_off, coef, out);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
+
+int mtl_spect_batch_noise(void* stream, const float* wav, const long* offsets, int K, int n_fft, int hop, const float* basis, int ldb, int F,
+                          float* out, int Tmax, int normalize, void* workspace, long workspace_bytes, const short* bank, long bank_len,
+                          const long* noise_off, const float* coef) {
+    if (!bank || !noise_off || !coef || bank_len <= 0) return MTL_EINVAL;
+    SpectP p = {};
+    p.wav = wav, p.offsets = offsets, p.basis = basis, p.out = out;
+    p.K = K, p.n_fft = n_fft, p.hop = hop, p.ldb = ldb, p.F = F, p.Tmax = Tmax;
+    p.bank = bank, p.bank_len = bank_len, p.noise_off = noise_off, p.coef = coef;
+    return spect_batch<true>(stream, p, normalize, workspace, workspace_bytes);
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@ contract of utils/data_loader.py:191-195 and the batch layout returned by `Spect
 """
 import csv
 import json
+import logging
+import os
 import unicodedata
 
 import numpy as np
@@ -136,13 +138,23 @@ class ManifestTaskDataset:
     `__getitem__` / `__len__` follow utils/data_loader.py:323-340 (validation / test use: manifest 0 only unless is_train)."""
 
     def __init__(self, vocab, args, manifest_filepath_list, feature_fn=None, partitions=None, seed=None, is_train=False,
-                 device_batches=False):
+                 device_batches=False, noise=None):
         """device_batches=True: `sample()` featurises each part (train / validation) with ONE `SpectrogramFrontEnd.batch` call and
         returns `inputs` on the device (the trainers copy device-resident inputs straight into their static buffers); the sizes,
         percentages and targets stay host tensors as `collate` makes them, and the index stream is the same.  The front-end is
-        built at the first `sample()`, so constructing the dataset needs no device.  `__getitem__` keeps the per-utterance path."""
+        built at the first `sample()`, so constructing the dataset needs no device.  `__getitem__` keeps the per-utterance path.
+
+        noise=(NoiseInjection, noise_prob): every utterance is featurised as SpectrogramParser.parse_audio does with a noise
+        injector (utils/data_loader.py:71-75).  The draws come from `self.rng`: `sample()` takes them per utterance in pick order
+        (train part, then validation part) right after the `choice` of the indices, for parts that `need` leaves out as well (the
+        number of draws does not depend on the audio, so all ranks keep one stream); `__getitem__` draws before it featurises.
+        noise_prob may be a string (the reference's --noise-prob has no type): float() is taken.  Not with a feature_fn, which
+        gets paths, not samples."""
         if device_batches and feature_fn is not None:
             raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
+        if noise is not None and feature_fn is not None:
+            raise NotImplementedError('noise injection mixes samples on the device: it cannot be combined with a feature_fn (which gets paths)')
+        self._noise = None if noise is None else (noise[0], float(noise[1]))
         self.device_batches, self._fe = device_batches, None
         self._fe_factory = lambda: SpectrogramFrontEnd(args.sample_rate, args.window_size, args.window_stride,
                                                        getattr(args, 'window', 'hamming'), True)
@@ -153,6 +165,7 @@ class ManifestTaskDataset:
             # meta_transfer_train.py:161), handed back on the host like the reference's parse_audio output
             fe = SpectrogramFrontEnd(args.sample_rate, args.window_size, args.window_stride, getattr(args, 'window', 'hamming'), True)
             feature_fn = lambda path: fe(load_wav_pcm16(path)).cpu()
+            self._fe = fe
         self.vocab, self.args, self.feature_fn = vocab, args, feature_fn
         self.ids_list = [read_manifest(p) for p in manifest_filepath_list]
         self.rng = np.random if seed is None else np.random.RandomState(seed)
@@ -170,24 +183,49 @@ class ManifestTaskDataset:
                 p = np.full(len(ids), 1 / len(ids))
             self.proba.append(p)
 
-    def _rows(self, ids, picks):
+    def _rows(self, ids, picks, draws=None):
         spects, trans = [], []
-        for j in picks:
+        for i, j in enumerate(picks):
             wav, txt = ids[j][0], ids[j][1]
-            spects.append(self.feature_fn(wav)[:, :self.args.src_max_len])
+            spects.append(self._feature(wav, None if draws is None else draws[i])[:, :self.args.src_max_len])
             trans.append(parse_transcript(self.vocab, txt))
         return spects, trans
+
+    def _feature(self, path, draw):
+        """per-utterance path: feature_fn(path), or for an utterance whose draw asks for noise `batch([y], noise=...)[0][0, 0]`, handed
+        back on the host like every feature; an utterance that `place` leaves clean (longer than its noise file) takes the clean path"""
+        if draw is None:
+            return self.feature_fn(path)
+        y = load_wav_pcm16(path)
+        placed = self._noise[0].place(draw, y.shape[0])
+        if placed is None:
+            return self.feature_fn(path)
+        plan = (self._noise[0], np.array([placed[0]], dtype=np.int64), np.array([placed[1]], dtype=np.float32))
+        return self._front_end().batch([y], noise=plan)[0][0, 0].cpu()
+
+    def _draws(self, n):
+        """the noise draws of n utterances, in order, from the dataset's stream (None without an injector)"""
+        if self._noise is None:
+            return None
+        return [self._noise[0].draw(self.rng, self._noise[1]) for _ in range(n)]
 
     def _front_end(self):
         if self._fe is None:
             self._fe = self._fe_factory()
         return self._fe
 
-    def _device_part(self, ids, picks):
-        """one part of a sampled batch through SpectrogramFrontEnd.batch: the 5-tuple of `collate` with `inputs` on the device"""
+    def _device_part(self, ids, picks, draws=None):
+        """one part of a sampled batch through SpectrogramFrontEnd.batch: the 5-tuple of `collate` with `inputs` on the device
+        (draws: one `plan` for the part, and the noisy form of the call unless every utterance stays clean)"""
         waves = [load_wav_pcm16(ids[j][0]) for j in picks]
         trans = [parse_transcript(self.vocab, ids[j][1]) for j in picks]
-        inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len)
+        noise_off = None
+        if draws is not None:
+            noise_off, level = self._noise[0].plan(draws, [w.shape[0] for w in waves])
+        if noise_off is not None and (noise_off >= 0).any():
+            inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len, noise=(self._noise[0], noise_off, level))
+        else:
+            inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len)
         k, max_t = len(trans), inputs.size(3)
         input_percentages = torch.zeros(k, dtype=torch.float32)
         targets = torch.full((k, max(len(t) for t in trans)), self.vocab.PAD_ID, dtype=torch.int64)
@@ -205,12 +243,14 @@ class ManifestTaskDataset:
         several ranks, only its own tasks' training batches."""
         ids = self.ids_list[manifest_id]
         picks = self.rng.choice(np.arange(0, len(ids)), k_train + k_val, p=self.proba[manifest_id], replace=True)
+        draws = self._draws(k_train + k_val)                         # (a part that is not needed has consumed its draws here)
+        dtr, dva = (None, None) if draws is None else (draws[:k_train], draws[k_train:k_train + k_val])
         if self.device_batches:
-            tr = self._device_part(ids, picks[:k_train]) if need[0] else None
-            va = self._device_part(ids, picks[k_train:k_train + k_val]) if need[1] else None
+            tr = self._device_part(ids, picks[:k_train], dtr) if need[0] else None
+            va = self._device_part(ids, picks[k_train:k_train + k_val], dva) if need[1] else None
             return tr, va
-        tr = collate(*self._rows(ids, picks[:k_train]), pad_id=self.vocab.PAD_ID) if need[0] else None
-        va = collate(*self._rows(ids, picks[k_train:k_train + k_val]), pad_id=self.vocab.PAD_ID) if need[1] else None
+        tr = collate(*self._rows(ids, picks[:k_train], dtr), pad_id=self.vocab.PAD_ID) if need[0] else None
+        va = collate(*self._rows(ids, picks[k_train:k_train + k_val], dva), pad_id=self.vocab.PAD_ID) if need[1] else None
         return tr, va
 
     def __len__(self):
@@ -223,7 +263,8 @@ class ManifestTaskDataset:
         else:
             ids = self.ids_list[0]
             row = ids[index % len(ids)]
-        return self.feature_fn(row[0])[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
+        draw = None if self._noise is None else self._draws(1)[0]
+        return self._feature(row[0], draw)[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
 
 
 class SpectrogramDataset(ManifestTaskDataset):
@@ -236,9 +277,13 @@ class SpectrogramDataset(ManifestTaskDataset):
     audio_conf: dict(sample_rate, window_size, window_stride, window, noise_dir, noise_prob, noise_levels) (:141-147).  Features come
     from the device front-end (SpectrogramFrontEnd = SpectrogramParser.parse_audio, :65-96) unless `feature_fn` is given.  Same
     attributes as the reference object (max_size, ids_list, proba, part_len, input_type, manifest_filepath_list, is_train) and the
-    same two console lines.  Outside the accelerated path and rejected loudly: augment=True (sox tempo / gain perturbation),
-    noise injection (audio_conf['noise_dir']), input_type other than 'char' (the bpe / ipa branches are commented out in the
-    reference too).  device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off)."""
+    same two console lines.  audio_conf['noise_dir'] builds a NoiseInjection over that directory (noise_levels, noise_prob as in
+    :60-63; its device part is lazy, so construction needs no device) and every parse_audio -- `sample()`, `__getitem__` of validation
+    and test loaders included, like the reference -- mixes noise on the device with probability noise_prob: see ManifestTaskDataset
+    (noise=) for the draw stream and NoiseInjection for the semantics.  noise_dir with a feature_fn raises NotImplementedError (a
+    feature function gets paths, not samples).  Outside the accelerated path and rejected loudly: augment=True (sox tempo / gain
+    perturbation), input_type other than 'char' (the bpe / ipa branches are commented out in the reference too).
+    device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off)."""
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
                  is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False):
@@ -246,8 +291,15 @@ class SpectrogramDataset(ManifestTaskDataset):
             raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
         if augment:
             raise NotImplementedError('augment=True (sox tempo / gain perturbation, utils/data_loader.py:28-38) is outside the accelerated path')
+        noise = None
         if audio_conf.get('noise_dir') is not None:
-            raise NotImplementedError("noise injection (audio_conf['noise_dir']) is outside the accelerated path")
+            if feature_fn is not None:
+                raise NotImplementedError("noise injection (audio_conf['noise_dir']) mixes samples on the device: it cannot be combined "
+                                          "with a feature_fn (which gets paths)")
+            self.noiseInjector = NoiseInjection(audio_conf['noise_dir'], audio_conf['sample_rate'], audio_conf.get('noise_levels', (0, 0.5)))
+            noise = (self.noiseInjector, float(audio_conf.get('noise_prob')))
+        else:
+            self.noiseInjector = None
         if input_type != 'char':
             raise NotImplementedError("only input_type='char' (utils/data_loader.py:342-361)")
         self.window_stride, self.window_size = audio_conf['window_stride'], audio_conf['window_size']
@@ -265,6 +317,7 @@ class SpectrogramDataset(ManifestTaskDataset):
             def feature_fn(path):
                 return front_end()(load_wav_pcm16(path)).cpu()
         super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
+        self._noise = noise                                          # (after the base constructor: the default feature_fn is no user's)
         self.device_batches, self._fe_factory = device_batches, front_end       # (sample() of a part: one front_end().batch call)
         self.manifest_filepath_list, self.input_type = manifest_filepath_list, input_type
         # (the reference leaves part_len at the LAST manifest's partition size, or max_size without partitions: :211-222)
@@ -277,7 +330,8 @@ class SpectrogramDataset(ManifestTaskDataset):
         return parse_transcript(self.vocab, transcript_path)
 
     def parse_audio(self, audio_path):
-        return self.feature_fn(audio_path)
+        """utils/data_loader.py:65-96: with a noise injector, one draw from the dataset's stream and the mix on the device"""
+        return self._feature(audio_path, None if self._noise is None else self._draws(1)[0])
 
 
 class BucketingSampler(torch.utils.data.Sampler):
@@ -425,6 +479,7 @@ class SpectrogramFrontEnd:
         self.consumer = consumer if consumer is not None or self.device.type != 'cuda' else torch.cuda.current_stream(self.device)
         self.stream = None                                     # batch()'s own stream, made at its first call
         self._pin_wav = self._pin_off = None                   # pinned staging of batch(), grown on demand
+        self._pin_noff = self._pin_lvl = None                  # ... and of its two noise tables
 
     def __call__(self, y):
         """y: 1-D float waveform (numpy or tensor) -> (F, T) fp32 tensor on the device, T = 1 + len(y) // hop."""
@@ -445,7 +500,7 @@ class SpectrogramFrontEnd:
                                         1 if self.normalize else 0), 'mtl_spect_logmag')
         return out
 
-    def batch(self, waves, max_frames=None):
+    def batch(self, waves, max_frames=None, noise=None):
         """K waveforms -> (inputs (K, 1, F, Tmax) fp32 on the device, input_sizes (K) int32 on the host): what `collate` builds from
         K `__call__` results cut to max_frames, in one device pass -- one pinned staging copy of the concatenated samples and of the
         offsets (two H2D copies) and the two launches of mtl_spect_batch (framing, STFT, log-magnitude, per-utterance statistics over
@@ -457,7 +512,14 @@ class SpectrogramFrontEnd:
         waits for them (no device-wide synchronisation).  `inputs.record_stream(consumer)` then tells the allocator that `consumer`
         reads the block: the trainer's host thread enqueues up to two iterations ahead, so the tensor is usually dropped while the
         trainer's copy of it is still pending -- without the record the next `batch` call could be handed the same memory and
-        overwrite it under that copy."""
+        overwrite it under that copy.
+
+        noise=(injector, noise_off, level), the output of `NoiseInjection.plan` for these K waveforms: utterance k is mixed with the
+        len(waves[k]) samples of the injector's device-resident int16 bank from noise_off[k] on (noise_off[k] < 0: clean) at
+        level[k], as NoiseInjection.inject_noise_sample does (utils/data_loader.py:383-399), while the samples are staged -- no mixed
+        waveform exists in memory and the host does not touch the samples.  The two tables (K int64, K float32) travel through
+        pinned staging like the offsets; the calls are mtl_wave_mix_coef, then mtl_spect_batch_noise, on the same stream under the
+        same event.  noise=None issues exactly the calls described above."""
         from . import _lib
         if self.device.type != 'cuda':
             raise RuntimeError('the spectrogram front-end runs on the MI355X only (no CPU fallback)')
@@ -477,6 +539,23 @@ class SpectrogramFrontEnd:
         # the staging buffers are free again: every earlier call waited for its copies before it returned
         self._pin_wav[:flat.shape[0]].copy_(torch.from_numpy(flat))
         self._pin_off[:K + 1].copy_(torch.from_numpy(offsets))
+        if noise is not None:
+            injector, noise_off, level = noise
+            noise_off, level = np.ascontiguousarray(noise_off, dtype=np.int64), np.ascontiguousarray(level, dtype=np.float32)
+            if noise_off.shape != (K,) or level.shape != (K,):
+                raise ValueError('batch: the noise plan has %s offsets and %s levels for %d waveforms' % (noise_off.shape, level.shape, K))
+            lengths = np.diff(offsets)
+            if ((noise_off >= 0) & (noise_off + lengths > injector.bank_len)).any():
+                raise ValueError('batch: a noise segment ends beyond the bank (%d samples)' % injector.bank_len)
+            bank = injector.device_bank(self.device)
+            cws_bytes = lib.mtl_wave_mix_coef_workspace(K)
+            if cws_bytes < 0:
+                raise RuntimeError('mtl_wave_mix_coef_workspace failed with code %d' % cws_bytes)
+            if self._pin_noff is None or self._pin_noff.numel() < K:
+                self._pin_noff = torch.empty(max(K, 64), dtype=torch.int64).pin_memory()
+                self._pin_lvl = torch.empty(max(K, 64), dtype=torch.float32).pin_memory()
+            self._pin_noff[:K].copy_(torch.from_numpy(noise_off))
+            self._pin_lvl[:K].copy_(torch.from_numpy(level))
         with torch.cuda.stream(self.stream):
             inputs = torch.empty(K, 1, self.F, tmax, device=self.device)
             d_wav = torch.empty(flat.shape[0], device=self.device)
@@ -484,11 +563,162 @@ class SpectrogramFrontEnd:
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
             d_wav.copy_(self._pin_wav[:flat.shape[0]], non_blocking=True)
             d_off.copy_(self._pin_off[:K + 1], non_blocking=True)
-            _lib.check(lib.mtl_spect_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
-                                           self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax, 1 if self.normalize else 0,
-                                           ws.data_ptr(), ws_bytes), 'mtl_spect_batch')
+            if noise is None:
+                _lib.check(lib.mtl_spect_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
+                                               self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax, 1 if self.normalize else 0,
+                                               ws.data_ptr(), ws_bytes), 'mtl_spect_batch')
+            else:
+                d_noff = torch.empty(K, dtype=torch.int64, device=self.device)
+                d_lvl = torch.empty(K, dtype=torch.float32, device=self.device)
+                coef = torch.empty(K, dtype=torch.float32, device=self.device)
+                cws = torch.empty(cws_bytes // 8, dtype=torch.float64, device=self.device)
+                d_noff.copy_(self._pin_noff[:K], non_blocking=True)
+                d_lvl.copy_(self._pin_lvl[:K], non_blocking=True)
+                _lib.check(lib.mtl_wave_mix_coef(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, bank.data_ptr(),
+                                                 injector.bank_len, d_noff.data_ptr(), d_lvl.data_ptr(), coef.data_ptr(), cws.data_ptr(),
+                                                 cws_bytes), 'mtl_wave_mix_coef')
+                _lib.check(lib.mtl_spect_batch_noise(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
+                                                     self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax,
+                                                     1 if self.normalize else 0, ws.data_ptr(), ws_bytes, bank.data_ptr(), injector.bank_len,
+                                                     d_noff.data_ptr(), coef.data_ptr()), 'mtl_spect_batch_noise')
             done = torch.cuda.Event()
             done.record(self.stream)
         done.synchronize()                                     # host wait on this stream's event only
         inputs.record_stream(self.consumer)
         return inputs, torch.from_numpy(frames)
+
+
+class NoiseInjection(object):
+    """utils/data_loader.py:367-399 with the mix on the device: `data += level * noise * rms(data) / rms(noise)`, `noise` being a
+    segment of a randomly chosen noise file as long as the utterance.  The reference's constructor plus `device` and `bank_gb`;
+    constructing needs no device (the device copy of the bank is made at first use and kept).  What the reference leaves to sox / soxi
+    is pinned here:
+
+      file list   `paths` = the sorted recursive list of *.wav under `path` (stands in for librosa.util.find_files).  Files are 16-bit
+                  PCM at `sample_rate`; channels are averaged as load_wav_pcm16 does and rounded back to int16.  Any other sample width
+                  or rate raises ValueError naming the file, a missing directory IOError (like the reference), an empty one ValueError,
+                  a corpus of more than `bank_gb` GiB ValueError.  All files live in ONE int16 array (`bank`) with per-file
+                  (`offsets`, `lengths`), in samples.
+      draws       draw(rng, noise_prob): binomial(1, noise_prob) and, only when it gave 1, in this order choice(paths),
+                  uniform(*noise_levels), rand() -- the reference's four draws (:73, :384-385, :391).
+      placement   in samples: start = floor(u * (N_file - n)), segment [start, start + n) -- equal lengths by construction (the
+                  reference hands seconds to `sox trim` and asserts the lengths afterwards).
+      too long    an utterance longer than the chosen noise file stays clean (the reference would fail its assert): its draws are
+                  consumed all the same, `skipped` is incremented and one logging.warning is issued per file.  A segment whose energy
+                  is exactly zero leaves the utterance clean as well (the reference would produce inf / nan).
+      arithmetic  S_d, S_n = sums of squares over the n samples in fp64, fixed order, no atomics; c = level * sqrt(S_d / n) /
+                  sqrt(S_n / n) in fp64, rounded once to fp32; mixed = fmaf(c, noise, data) in fp32 with noise = (float)int16 / 32768
+                  (exact).  Every kernel that mixes uses this one expression: fused and unfused paths agree bit for bit."""
+
+    def __init__(self, path=None, sample_rate=16000, noise_levels=(0, 0.5), device='cuda', bank_gb=8.0):
+        import glob
+        import wave
+        if path is None or not os.path.exists(path):
+            print("Directory doesn't exist: {}".format(path))
+            raise IOError("Directory doesn't exist: {}".format(path))
+        self.paths = sorted(glob.glob(os.path.join(glob.escape(path), '**', '*.wav'), recursive=True))
+        if not self.paths:
+            raise ValueError('NoiseInjection: no *.wav file under %s' % path)
+        self.sample_rate, self.noise_levels, self.device = sample_rate, tuple(noise_levels), torch.device(device)
+        self.skipped, self._warned, self._bank = 0, set(), None
+        lengths = []
+        for p in self.paths:                                   # headers first: the bank limit is checked before anything is read
+            with wave.open(p, 'rb') as w:
+                if w.getsampwidth() != 2:
+                    raise ValueError('NoiseInjection: %s has %d-byte samples, only 16-bit PCM is supported' % (p, w.getsampwidth()))
+                if w.getframerate() != sample_rate:
+                    raise ValueError('NoiseInjection: %s is sampled at %d Hz, the front-end at %d Hz (no resampling here)'
+                                     % (p, w.getframerate(), sample_rate))
+                lengths.append(w.getnframes())
+        self.lengths = np.array(lengths, dtype=np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.bank_len = int(self.lengths.sum())
+        if self.bank_len == 0:
+            raise ValueError('NoiseInjection: the *.wav files under %s hold no samples' % path)
+        if 2 * self.bank_len > bank_gb * 2 ** 30:
+            raise ValueError('NoiseInjection: the noise corpus under %s takes %.3f GiB as int16, more than bank_gb=%g'
+                             % (path, 2 * self.bank_len / 2.0 ** 30, bank_gb))
+        self.bank = np.empty(self.bank_len, dtype=np.int16)
+        for p, o, n in zip(self.paths, self.offsets, self.lengths):
+            with wave.open(p, 'rb') as w:
+                ch = w.getnchannels()
+                raw = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
+            if ch > 1:                                         # load_wav_pcm16's channel mean (fp32), back on the int16 grid
+                mean = (raw.astype(np.float32) / 32768.0).reshape(-1, ch).mean(axis=1).astype(np.float32)
+                raw = np.clip(np.rint(mean * 32768.0), -32768, 32767).astype(np.int16)
+            self.bank[o:o + n] = raw
+
+    def device_bank(self, device=None):
+        """the int16 bank on the device: uploaded at the first call and kept"""
+        if self._bank is None:
+            dev = torch.device(device) if device is not None else self.device
+            if dev.type != 'cuda':
+                raise RuntimeError('noise is mixed on the MI355X only (no CPU fallback)')
+            self._bank = torch.from_numpy(self.bank).to(dev)
+        return self._bank
+
+    def draw(self, rng, noise_prob):
+        """None (clean) | (file_index, level, u): binomial, then -- only if it gave 1 -- choice, uniform, rand, from `rng`"""
+        if not rng.binomial(1, float(noise_prob)):
+            return None
+        path = rng.choice(self.paths)
+        level = rng.uniform(*self.noise_levels)
+        return self.paths.index(path), float(level), float(rng.rand())
+
+    def place(self, draw, n_samples):
+        """(bank_offset, level) of the segment [start, start + n_samples) of the drawn file, start = floor(u * (N_file - n_samples));
+        None for a clean draw and for an utterance longer than the file (counted in `skipped`, one warning per file)"""
+        if draw is None:
+            return None
+        fi, level, u = draw
+        room = int(self.lengths[fi]) - int(n_samples)
+        if room < 0:
+            self.skipped += 1
+            if fi not in self._warned:
+                self._warned.add(fi)
+                logging.warning('NoiseInjection: %s (%d samples) is shorter than an utterance of %d samples: such utterances stay clean',
+                                self.paths[fi], int(self.lengths[fi]), int(n_samples))
+            return None
+        start = min(int(np.floor(u * room)), room)
+        return int(self.offsets[fi]) + start, level
+
+    def plan(self, draws, lengths):
+        """K draws and the K utterance lengths -> (noise_off int64 (K), level float32 (K)); noise_off = -1 for a clean utterance"""
+        noise_off, level = np.full(len(draws), -1, dtype=np.int64), np.zeros(len(draws), dtype=np.float32)
+        for k, (d, n) in enumerate(zip(draws, lengths)):
+            placed = self.place(d, n)
+            if placed is not None:
+                noise_off[k], level[k] = placed
+        return noise_off, level
+
+    def inject_noise(self, data):
+        """utils/data_loader.py:383-386, draws from the global np.random like the reference"""
+        noise_path = np.random.choice(self.paths)
+        noise_level = np.random.uniform(*self.noise_levels)
+        return self.inject_noise_sample(data, noise_path, noise_level)
+
+    def inject_noise_sample(self, data, noise_path, noise_level, u=None):
+        """utils/data_loader.py:388-399 on the device: mtl_wave_mix_coef and one mtl_wave_mix call with K = 1 -> the mixed waveform as
+        float32 numpy (`data` itself is left alone).  u=None draws np.random.rand() as the reference does."""
+        from . import _lib
+        if u is None:
+            u = np.random.rand()
+        y = np.ascontiguousarray(data.detach().cpu() if torch.is_tensor(data) else data, dtype=np.float32).reshape(-1)
+        placed = self.place((self.paths.index(str(noise_path)), float(noise_level), float(u)), y.shape[0])
+        if placed is None or y.shape[0] == 0:
+            return y.copy()
+        lib, bank = _lib.lib(), self.device_bank()
+        dev = bank.device
+        wav = torch.from_numpy(y).to(dev)
+        off = torch.tensor([0, y.shape[0]], dtype=torch.int64, device=dev)
+        noff = torch.tensor([placed[0]], dtype=torch.int64, device=dev)
+        lvl = torch.tensor([placed[1]], dtype=torch.float32, device=dev)
+        coef, out = torch.empty(1, device=dev), torch.empty_like(wav)
+        ws_bytes = lib.mtl_wave_mix_coef_workspace(1)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.mtl_wave_mix_coef(st, wav.data_ptr(), off.data_ptr(), 1, bank.data_ptr(), self.bank_len, noff.data_ptr(),
+                                         lvl.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws_bytes), 'mtl_wave_mix_coef')
+        _lib.check(lib.mtl_wave_mix(st, wav.data_ptr(), off.data_ptr(), 1, bank.data_ptr(), self.bank_len, noff.data_ptr(),
+                                    coef.data_ptr(), out.data_ptr()), 'mtl_wave_mix')
+        return out.cpu().numpy()

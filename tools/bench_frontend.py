@@ -12,6 +12,17 @@ alternate, and the figure is the median of `--reps` calls after `--warmup`.  Als
 mtl_spect_batch alone (operands already on the device).
 
     python tools/bench_frontend.py [--reps 20] [--warmup 3] [--queued-ms 100] [--out profiles/frontend_batch.json]
+
+--noise-out PATH runs the noise-injection leg instead, same protocol, three paths that alternate:
+
+  (a) clean:      `batch(waves)`
+  (b) host mix:   the reference's mix (utils/data_loader.py:396-398) in numpy on the calling thread, then `batch(mixed)`
+  (c) device mix: `batch(waves, noise=plan)`, every utterance noisy
+
+over a seeded noise corpus of four 30-second files written to a temporary directory, plus the HIP-event times of mtl_spect_batch,
+mtl_spect_batch_noise and mtl_wave_mix_coef alone.
+
+    python tools/bench_frontend.py --noise-out profiles/frontend_noise.json
 """
 import argparse
 import json
@@ -41,6 +52,7 @@ def main():
     ap.add_argument('--samples', type=int, default=160000)
     ap.add_argument('--queued-ms', type=float, default=100.0)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--noise-out', default=None)
     a = ap.parse_args()
     if a.reps < 20 or a.warmup < 3:
         ap.error('at least 20 timed calls after at least 3 warm-ups')
@@ -52,6 +64,8 @@ def main():
     labels = [[4, 5]] * K
     fe = mtl_amd.SpectrogramFrontEnd(16000, 0.02, 0.01, 'hamming', normalize=True)
     dev = fe.device
+    if a.noise_out:
+        return noise_leg(a, mtl_amd, _lib, fe, waves)
 
     def per_utterance():
         specs = [fe(y).cpu() for y in waves]
@@ -137,6 +151,117 @@ def main():
         with open(a.out, 'w') as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write('\n')
+
+
+def noise_leg(a, mtl_amd, _lib, fe, waves):
+    import tempfile
+    import wave
+    K, dev = len(waves), fe.device
+    with tempfile.TemporaryDirectory() as d:
+        for i in range(4):
+            with wave.open(os.path.join(d, 'noise%d.wav' % i), 'wb') as w:
+                w.setnchannels(1)
+                w.setsampwidth(2)
+                w.setframerate(16000)
+                w.writeframes((np.clip(waveform(3 * a.samples, 900 + i)[::-1], -1, 1) * 32767).astype('<i2').tobytes())
+        inj = mtl_amd.NoiseInjection(d, 16000, (0.1, 0.5))
+    rng = np.random.RandomState(1)
+    plan = inj.plan([inj.draw(rng, 1.0) for _ in range(K)], [len(y) for y in waves])
+    assert (plan[0] >= 0).all()
+
+    def clean():
+        return fe.batch(waves)[0]
+
+    def host_mix():
+        mixed = []
+        for y, o, lv in zip(waves, plan[0], plan[1]):
+            n = inj.bank[o:o + len(y)].astype(np.float32) / np.float32(32768.0)
+            noise_energy, data_energy = np.sqrt(n.dot(n) / n.size), np.sqrt(y.dot(y) / y.size)
+            mixed.append(y + lv * n * data_energy / noise_energy)
+        return fe.batch(mixed)[0]
+
+    def device_mix():
+        return fe.batch(waves, noise=(inj,) + plan)[0]
+
+    xa, xb, xc = clean(), host_mix(), device_mix()
+    torch.cuda.synchronize()
+    worst = max(float((xc[k].double() - xb[k].double()).norm() / xb[k].double().norm()) for k in range(K))
+    moved = min(float((xc[k].double() - xa[k].double()).norm() / xa[k].double().norm()) for k in range(K))
+    assert xb.shape == xc.shape and worst < 2e-5 and moved > 1e-3, (worst, moved)
+
+    m = torch.randn(4096, 4096, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        m @ m
+    e0.record()
+    for _ in range(20):
+        m @ m
+    e1.record()
+    torch.cuda.synchronize()
+    chain = max(int(round(a.queued_ms / (e0.elapsed_time(e1) / 20))), 1)
+
+    def timed(fn, busy):
+        torch.cuda.synchronize()
+        if busy:
+            for _ in range(chain):
+                m @ m
+        t0 = time.perf_counter()
+        x = fn()
+        dt = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        del x
+        return dt
+
+    paths = (('clean', clean), ('host_mix', host_mix), ('device_mix', device_mix))
+    times = {(name, busy): [] for name, _ in paths for busy in (False, True)}
+    for rep in range(a.warmup + a.reps):
+        for busy in (False, True):
+            for name, fn in paths:
+                dt = timed(fn, busy)
+                if rep >= a.warmup:
+                    times[(name, busy)].append(dt)
+
+    # device time of the launches alone (operands on the device)
+    lib = _lib.lib()
+    flat, offsets, frames, tmax = mtl_amd.pack_waveforms(waves, fe.hop, fe.n_fft)
+    d_wav, d_off = torch.from_numpy(flat).to(dev), torch.from_numpy(offsets).to(dev)
+    d_noff, d_lvl = torch.from_numpy(plan[0]).to(dev), torch.from_numpy(plan[1]).to(dev)
+    bank, coef = inj.device_bank(), torch.empty(K, device=dev)
+    out = torch.empty(K, 1, fe.F, tmax, device=dev)
+    ws_bytes, cws_bytes = lib.mtl_spect_batch_workspace(int(frames.sum()), K, fe.F), lib.mtl_wave_mix_coef_workspace(K)
+    ws, cws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev), torch.empty(cws_bytes // 8, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    spect = (st, d_wav.data_ptr(), d_off.data_ptr(), K, fe.n_fft, fe.hop, fe.basis.data_ptr(), fe.ldb, fe.F, out.data_ptr(), tmax, 1,
+             ws.data_ptr(), ws_bytes)
+    calls = dict(
+        spect_batch=lambda: lib.mtl_spect_batch(*spect),
+        wave_mix_coef=lambda: lib.mtl_wave_mix_coef(st, d_wav.data_ptr(), d_off.data_ptr(), K, bank.data_ptr(), inj.bank_len, d_noff.data_ptr(),
+                                                    d_lvl.data_ptr(), coef.data_ptr(), cws.data_ptr(), cws_bytes),
+        spect_batch_noise=lambda: lib.mtl_spect_batch_noise(*(spect + (bank.data_ptr(), inj.bank_len, d_noff.data_ptr(), coef.data_ptr()))))
+    launch_us = {name: [] for name in calls}
+    for rep in range(a.warmup + a.reps):
+        for name in ('wave_mix_coef', 'spect_batch', 'spect_batch_noise'):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(calls[name](), name)
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                launch_us[name].append(1e3 * e0.elapsed_time(e1))
+
+    key = lambda n, b: '%s_%s' % (n, 'busy' if b else 'idle')
+    res = dict(device=torch.cuda.get_device_name(0), utterances=K, samples_per_utterance=a.samples, reps=a.reps, warmup=a.warmup,
+               queued_ms=a.queued_ms, queued_products=chain, bank_samples=inj.bank_len, worst_rel_device_vs_host_mix=worst,
+               least_rel_noisy_vs_clean=moved,
+               utt_per_s={key(n, b): K / statistics.median(v) for (n, b), v in times.items()},
+               call_ms_median={key(n, b): 1e3 * statistics.median(v) for (n, b), v in times.items()},
+               call_ms_min_max={key(n, b): [1e3 * min(v), 1e3 * max(v)] for (n, b), v in times.items()},
+               launches_us_median={n: statistics.median(v) for n, v in launch_us.items()},
+               launches_us_min={n: min(v) for n, v in launch_us.items()})
+    print(json.dumps(res))
+    with open(a.noise_out, 'w') as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write('\n')
 
 
 if __name__ == '__main__':
