@@ -431,6 +431,26 @@ int mtl_wave_mix(void* stream, const float* wav, const long* offsets, int K, con
 int mtl_spect_batch_noise(void* stream, const float* wav, const long* offsets, int K, int n_fft, int hop, const float* basis, int ldb, int F,
                           float* out, int Tmax, int normalize, void* workspace, long workspace_bytes, const short* bank, long bank_len,
                           const long* noise_off, const float* coef);
+/* Tempo and gain augmentation on the device (load_randomly_augmented_audio, utils/audio.py:35-61: `sox tempo f gain g` into a 16-bit
+ * file), in front of the calls above (csrc/mtl_tempo.hip).  sox is not reproduced sample for sample (it dithers): the behaviour is DEFINED
+ * here and in DESIGN.md section 12, parity unpinned.  wav / offsets as in mtl_spect_batch (utterance k: L_k samples, read as 0 at and
+ * beyond L_k); out_offsets: K + 1 int64, the stretched utterance k has N_k = out_offsets[k+1] - out_offsets[k] samples (the caller's
+ * N_k = floor(L_k / f_k + 0.5), or L_k for f_k == 1); tempo: K doubles f_k.  WSOLA with segment `seg`, search `search`, overlap `overlap`
+ * samples (1 <= overlap <= 256, 0 <= search <= 255, seg > overlap), H = seg - overlap: M_k = ceil(N_k / H) segments, segment m starts at
+ * p_m = floor(f (m H) + 0.5) (IEEE fp64, one multiply, one add) shifted by o_m in [0, search]; o_0 = search / 2, o_m = the c that
+ * minimises sum_{i < overlap} (tail_{m-1}[i] - x[p_m + c + i])^2, tail_{m-1}[i] = x[p_{m-1} + o_{m-1} + H + i], fp64 sums in index order,
+ * the smallest c on a tie.  seg_base: K + 1 int64, utterance k owns seg_off[seg_base[k] .. seg_base[k+1]) (>= M_k entries; f_k == 1.0:
+ * the effect is bypassed, none are written or read).  1 <= K <= 2^20.  No workspace, no atomics: bitwise repeatable.
+ *   mtl_tempo_search: seg_off[seg_base[k] + m] = o_m.  One workgroup per utterance walks the chain (tail_m depends on o_m). */
+int mtl_tempo_search(void* stream, const float* wav, const long* offsets, const long* out_offsets, const double* tempo, const long* seg_base,
+                     int K, int seg, int search, int overlap, int* seg_off);
+/*   mtl_tempo_render: out[out_offsets[k] + m H + i] (i < H) = x[p_m + o_m + i], and for m >= 1, i < overlap the cross-fade
+ *     fmaf(i / overlap, x[p_m + o_m + i] - tail_{m-1}[i], tail_{m-1}[i]) in fp32; f_k == 1.0 copies.  quantize != 0: every sample t then
+ *     becomes clip(rint(t gain[k] 32768), -32768, 32767) / 32768 (gain: K floats, linear; the 16-bit file without dither);
+ *     quantize == 0: the raw overlap-add, gain (nullable) is not read.  Table entries are clamped into [0, search]: a wrong table
+ *     cannot read out of bounds.  out has sum of N_k floats. */
+int mtl_tempo_render(void* stream, const float* wav, const long* offsets, const long* out_offsets, const double* tempo, const float* gain,
+                     const long* seg_base, const int* seg_off, int K, int seg, int search, int overlap, int quantize, float* out);
 
 /* ---- LSTM cell, one time step (lm/model/rnn_model.py:20 nn.LSTM; lm/main_meta_transfer.py:277-411) ----------
  * gx = x_t . W_ih^T + b_ih and gh = h_{t-1} . W_hh^T + b_hh come from mtl_gemm_f32_ex (B x 4H each, torch gate order i|f|g|o).

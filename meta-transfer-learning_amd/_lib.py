@@ -117,6 +117,8 @@ SIGNATURES = {
     'mtl_wave_mix_coef': (I, [P, P, P, I, P, L, P, P, P, P, L]),
     'mtl_wave_mix': (I, [P, P, P, I, P, L, P, P, P]),
     'mtl_spect_batch_noise': (I, [P, P, P, I, I, I, P, I, I, P, I, I, P, L, P, L, P, P]),
+    'mtl_tempo_search': (I, [P, P, P, P, P, P, I, I, I, I, P]),
+    'mtl_tempo_render': (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     'mtl_lstm_cell_fwd': (I, [P, P, P, P, P, P, P, P, P, F, I, I]),
     'mtl_lstm_cell_bwd': (I, [P, P, P, F, P, P, P, P, P, P, P, I, I]),
     'mtl_lstm_layer_supported': (I, [I, I]),

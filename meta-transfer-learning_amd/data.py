@@ -138,7 +138,7 @@ class ManifestTaskDataset:
     `__getitem__` / `__len__` follow utils/data_loader.py:323-340 (validation / test use: manifest 0 only unless is_train)."""
 
     def __init__(self, vocab, args, manifest_filepath_list, feature_fn=None, partitions=None, seed=None, is_train=False,
-                 device_batches=False, noise=None):
+                 device_batches=False, noise=None, augment=None):
         """device_batches=True: `sample()` featurises each part (train / validation) with ONE `SpectrogramFrontEnd.batch` call and
         returns `inputs` on the device (the trainers copy device-resident inputs straight into their static buffers); the sizes,
         percentages and targets stay host tensors as `collate` makes them, and the index stream is the same.  The front-end is
@@ -149,12 +149,23 @@ class ManifestTaskDataset:
         (train part, then validation part) right after the `choice` of the indices, for parts that `need` leaves out as well (the
         number of draws does not depend on the audio, so all ranks keep one stream); `__getitem__` draws before it featurises.
         noise_prob may be a string (the reference's --noise-prob has no type): float() is taken.  Not with a feature_fn, which
-        gets paths, not samples."""
+        gets paths, not samples.
+
+        augment=TempoGainAugment(...): every utterance is loaded as load_randomly_augmented_audio does (utils/audio.py:50-61: a random
+        tempo, then a random gain, then the 16-bit file) before anything else happens to it, on the device, in the batched path only
+        (device_batches=True; not with a feature_fn).  Per utterance the stream yields tempo, gain and THEN that utterance's noise
+        draws, as parse_audio interleaves them (utils/data_loader.py:67-75); the noise segment is as long as the STRETCHED utterance.
+        A part that `need` leaves out consumes these draws too.  augment=None leaves the stream exactly as it is without."""
         if device_batches and feature_fn is not None:
             raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
         if noise is not None and feature_fn is not None:
             raise NotImplementedError('noise injection mixes samples on the device: it cannot be combined with a feature_fn (which gets paths)')
+        if augment is not None and feature_fn is not None:
+            raise NotImplementedError('tempo / gain augmentation runs on the device: it cannot be combined with a feature_fn (which gets paths)')
+        if augment is not None and not device_batches:
+            raise NotImplementedError('tempo / gain augmentation exists in the batched device path only: pass device_batches=True')
         self._noise = None if noise is None else (noise[0], float(noise[1]))
+        self._augment = augment
         self.device_batches, self._fe = device_batches, None
         self._fe_factory = lambda: SpectrogramFrontEnd(args.sample_rate, args.window_size, args.window_stride,
                                                        getattr(args, 'window', 'hamming'), True)
@@ -192,22 +203,33 @@ class ManifestTaskDataset:
         return spects, trans
 
     def _feature(self, path, draw):
-        """per-utterance path: feature_fn(path), or for an utterance whose draw asks for noise `batch([y], noise=...)[0][0, 0]`, handed
-        back on the host like every feature; an utterance that `place` leaves clean (longer than its noise file) takes the clean path"""
-        if draw is None:
+        """per-utterance path: feature_fn(path), or for an utterance whose draw = (augmentation, noise) asks for either
+        `batch([y], augment=..., noise=...)[0][0, 0]`, handed back on the host like every feature; an utterance that `place` leaves clean
+        (longer than its noise file) and is not augmented takes the clean path"""
+        if draw is None or (draw[0] is None and draw[1] is None):
             return self.feature_fn(path)
         y = load_wav_pcm16(path)
-        placed = self._noise[0].place(draw, y.shape[0])
-        if placed is None:
+        kw, n = {}, y.shape[0]
+        if draw[0] is not None:
+            tempo, gain_db, out_lengths = self._augment.plan([draw[0]], [n])
+            kw['augment'], n = (tempo, gain_db), int(out_lengths[0])
+        placed = None if draw[1] is None else self._noise[0].place(draw[1], n)
+        if placed is not None:
+            kw['noise'] = (self._noise[0], np.array([placed[0]], dtype=np.int64), np.array([placed[1]], dtype=np.float32))
+        if not kw:
             return self.feature_fn(path)
-        plan = (self._noise[0], np.array([placed[0]], dtype=np.int64), np.array([placed[1]], dtype=np.float32))
-        return self._front_end().batch([y], noise=plan)[0][0, 0].cpu()
+        return self._front_end().batch([y], **kw)[0][0, 0].cpu()
 
     def _draws(self, n):
-        """the noise draws of n utterances, in order, from the dataset's stream (None without an injector)"""
-        if self._noise is None:
+        """the draws of n utterances, in order, from the dataset's stream: per utterance (augmentation draw | None, noise draw | None),
+        tempo and gain before that utterance's noise draws (None without an augmentation and an injector)"""
+        if self._noise is None and self._augment is None:
             return None
-        return [self._noise[0].draw(self.rng, self._noise[1]) for _ in range(n)]
+        out = []
+        for _ in range(n):
+            aug = None if self._augment is None else self._augment.draw(self.rng)
+            out.append((aug, None if self._noise is None else self._noise[0].draw(self.rng, self._noise[1])))
+        return out
 
     def _front_end(self):
         if self._fe is None:
@@ -216,16 +238,19 @@ class ManifestTaskDataset:
 
     def _device_part(self, ids, picks, draws=None):
         """one part of a sampled batch through SpectrogramFrontEnd.batch: the 5-tuple of `collate` with `inputs` on the device
-        (draws: one `plan` for the part, and the noisy form of the call unless every utterance stays clean)"""
+        (draws: one augmentation `plan` and one noise `plan` -- on the stretched lengths -- for the part; the noisy form of the call
+        unless every utterance stays clean)"""
         waves = [load_wav_pcm16(ids[j][0]) for j in picks]
         trans = [parse_transcript(self.vocab, ids[j][1]) for j in picks]
-        noise_off = None
-        if draws is not None:
-            noise_off, level = self._noise[0].plan(draws, [w.shape[0] for w in waves])
-        if noise_off is not None and (noise_off >= 0).any():
-            inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len, noise=(self._noise[0], noise_off, level))
-        else:
-            inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len)
+        kw, lengths = {}, [w.shape[0] for w in waves]
+        if draws is not None and self._augment is not None:
+            tempo, gain_db, lengths = self._augment.plan([d[0] for d in draws], lengths)
+            kw['augment'] = (tempo, gain_db)
+        if draws is not None and self._noise is not None:
+            noise_off, level = self._noise[0].plan([d[1] for d in draws], lengths)
+            if (noise_off >= 0).any():
+                kw['noise'] = (self._noise[0], noise_off, level)
+        inputs, input_sizes = self._front_end().batch(waves, max_frames=self.args.src_max_len, **kw)
         k, max_t = len(trans), inputs.size(3)
         input_percentages = torch.zeros(k, dtype=torch.float32)
         targets = torch.full((k, max(len(t) for t in trans)), self.vocab.PAD_ID, dtype=torch.int64)
@@ -263,8 +288,8 @@ class ManifestTaskDataset:
         else:
             ids = self.ids_list[0]
             row = ids[index % len(ids)]
-        draw = None if self._noise is None else self._draws(1)[0]
-        return self._feature(row[0], draw)[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
+        draws = self._draws(1)
+        return self._feature(row[0], None if draws is None else draws[0])[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
 
 
 class SpectrogramDataset(ManifestTaskDataset):
@@ -281,16 +306,24 @@ class SpectrogramDataset(ManifestTaskDataset):
     :60-63; its device part is lazy, so construction needs no device) and every parse_audio -- `sample()`, `__getitem__` of validation
     and test loaders included, like the reference -- mixes noise on the device with probability noise_prob: see ManifestTaskDataset
     (noise=) for the draw stream and NoiseInjection for the semantics.  noise_dir with a feature_fn raises NotImplementedError (a
-    feature function gets paths, not samples).  Outside the accelerated path and rejected loudly: augment=True (sox tempo / gain
-    perturbation), input_type other than 'char' (the bpe / ipa branches are commented out in the reference too).
+    feature function gets paths, not samples).  augment=True (load_randomly_augmented_audio in parse_audio, utils/data_loader.py:67-70)
+    builds a TempoGainAugment with the reference's ranges: tempo and gain are applied on the device in the batched path, so it needs
+    device_batches=True -- without it, and with a feature_fn, augment=True raises NotImplementedError.  See ManifestTaskDataset (augment=)
+    for the draw stream and TempoGainAugment for the semantics (a restatement of ours: sox is not reproduced sample for sample).
+    Outside the accelerated path and rejected loudly: input_type other than 'char' (the bpe / ipa branches are commented out in the
+    reference too).
     device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off)."""
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
                  is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False):
         if device_batches and feature_fn is not None:
             raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
-        if augment:
-            raise NotImplementedError('augment=True (sox tempo / gain perturbation, utils/data_loader.py:28-38) is outside the accelerated path')
+        if augment and feature_fn is not None:
+            raise NotImplementedError('augment=True (tempo / gain perturbation, utils/data_loader.py:28-38) runs on the device: it cannot '
+                                      'be combined with a feature_fn (which gets paths)')
+        if augment and not device_batches:
+            raise NotImplementedError('augment=True (tempo / gain perturbation, utils/data_loader.py:28-38) exists in the batched device '
+                                      'path only: pass device_batches=True')
         noise = None
         if audio_conf.get('noise_dir') is not None:
             if feature_fn is not None:
@@ -318,6 +351,7 @@ class SpectrogramDataset(ManifestTaskDataset):
                 return front_end()(load_wav_pcm16(path)).cpu()
         super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
         self._noise = noise                                          # (after the base constructor: the default feature_fn is no user's)
+        self._augment = TempoGainAugment() if augment else None
         self.device_batches, self._fe_factory = device_batches, front_end       # (sample() of a part: one front_end().batch call)
         self.manifest_filepath_list, self.input_type = manifest_filepath_list, input_type
         # (the reference leaves part_len at the LAST manifest's partition size, or max_size without partitions: :211-222)
@@ -330,8 +364,10 @@ class SpectrogramDataset(ManifestTaskDataset):
         return parse_transcript(self.vocab, transcript_path)
 
     def parse_audio(self, audio_path):
-        """utils/data_loader.py:65-96: with a noise injector, one draw from the dataset's stream and the mix on the device"""
-        return self._feature(audio_path, None if self._noise is None else self._draws(1)[0])
+        """utils/data_loader.py:65-96: with augmentation and / or a noise injector, this utterance's draws from the dataset's stream and
+        the work on the device"""
+        draws = self._draws(1)
+        return self._feature(audio_path, None if draws is None else draws[0])
 
 
 class BucketingSampler(torch.utils.data.Sampler):
@@ -450,6 +486,133 @@ def pack_waveforms(waves, hop, n_fft, max_frames=None):
     return np.concatenate(arrs), offsets, frames, int(frames.max())
 
 
+def wsola_geometry(sample_rate):
+    """(segment S, search R, overlap O) in samples of the tempo change at `sample_rate`: 82 ms, 14.68 ms and 12 ms, the defaults that the
+    documentation of sox's `tempo` effect gives, rounded as S = floor(sr 0.082 + 0.5), R = floor(sr 0.01468 + 0.5),
+    O = max(floor(sr 0.012 + 4.5), 16) rounded down to a multiple of 8: (1312, 235, 192) at 16 kHz, (656, 117, 96) at 8 kHz."""
+    S = int(np.floor(sample_rate * 0.082 + 0.5))
+    R = int(np.floor(sample_rate * 0.01468 + 0.5))
+    O = max(int(np.floor(sample_rate * 0.012 + 4.5)), 16) // 8 * 8
+    return S, R, O
+
+
+class TempoGainAugment(object):
+    """load_randomly_augmented_audio (utils/audio.py:35-61) with the work on the device: a random tempo in `tempo_range` (pitch kept), then
+    a random gain in `gain_range` dB, then the 16-bit file the reference reads back.  Pure numpy: the device part is
+    `SpectrogramFrontEnd.batch(augment=)` / `tempo_gain`.  The reference shells out to `sox`, which is no dependency of this project and dithers
+    randomly when it writes 16 bits, so the behaviour is DEFINED by the restatement below, parity with sox unpinned (as with librosa in
+    the front-end and `sox trim` in NoiseInjection); tests/augment_util.py holds it in numpy and fp64, DESIGN.md section 12 the reasons.
+
+      draws       draw(rng): uniform(*tempo_range), then uniform(*gain_range) -- the reference's two draws, in its order; both reach sox
+                  through "{:.3f}".format, so the values used are float('%.3f' % v).
+      tempo f     WSOLA with `wsola_geometry(sample_rate)` = (S, R, O), H = S - O.  L samples become N = floor(L / f + 0.5) in
+                  M = ceil(N / H) segments; segment m starts in the input at p_m = floor(f (m H) + 0.5) (fp64) shifted by o_m in [0, R]:
+                  o_0 = R // 2, and for m >= 1 the c minimising sum_{i<O} (tail_{m-1}[i] - x[p_m + c + i])^2 over ALL R + 1 candidates
+                  (fp64, the smallest c on a tie), tail_{m-1}[i] = x[p_{m-1} + o_{m-1} + H + i]; reads at or beyond L give 0.  Output
+                  sample m H + i (i < H) is x[p_m + o_m + i], for m >= 1 and i < O cross-faded in fp32 as
+                  tail_{m-1}[i] + (i / O) (x[p_m + o_m + i] - tail_{m-1}[i]).  f == 1.0 bypasses the effect (N = L, a copy), as sox does.
+      gain, file  y = clip(rint(t g 32768), -32768, 32767) / 32768 with g = (float)10^(gain_db / 20) formed in fp64 and rounded once:
+                  sox's 16-bit output without its dither, gain after tempo as in the reference's effect chain (+8 dB does clip)."""
+
+    def __init__(self, tempo_range=(0.85, 1.15), gain_range=(-6, 8)):
+        self.tempo_range, self.gain_range = tuple(tempo_range), tuple(gain_range)
+
+    def draw(self, rng):
+        """(tempo, gain_db), both rounded to three decimals: uniform(*tempo_range), then uniform(*gain_range), from `rng`"""
+        tempo = rng.uniform(low=self.tempo_range[0], high=self.tempo_range[1])
+        gain = rng.uniform(low=self.gain_range[0], high=self.gain_range[1])
+        return float('{:.3f}'.format(tempo)), float('{:.3f}'.format(gain))
+
+    @staticmethod
+    def out_length(n_samples, tempo):
+        """N = floor(L / tempo + 0.5); L itself for tempo == 1.0 (the bypass)"""
+        if not tempo > 0.0:
+            raise ValueError('TempoGainAugment: a tempo factor must be positive, got %r' % (tempo,))
+        return int(n_samples) if tempo == 1.0 else int(np.floor(int(n_samples) / float(tempo) + 0.5))
+
+    def plan(self, draws, lengths):
+        """K draws and the K utterance lengths -> (tempo float64 (K), gain_db float32 (K), out_lengths int64 (K))"""
+        tempo = np.array([d[0] for d in draws], dtype=np.float64)
+        gain_db = np.array([d[1] for d in draws], dtype=np.float32)
+        out_lengths = np.array([self.out_length(n, t) for n, t in zip(lengths, tempo)], dtype=np.int64)
+        return tempo, gain_db, out_lengths
+
+
+def tempo_gain_tables(waves, tempo, gain_db, sample_rate):
+    """host side of the tempo / gain calls, pure numpy: dict(flat float32 (sum of L_k), offsets int64 (K + 1), out_offsets int64 (K + 1)
+    from N_k = TempoGainAugment.out_length, seg_base int64 (K + 1): the prefix of the segments per utterance (ceil(N_k / H); none for
+    tempo 1.0), tempo float64 (K), gain float32 (K): (float)10^(gain_db / 20), geometry (S, R, O))"""
+    if len(waves) == 0:
+        raise ValueError('tempo_gain_tables: an empty list of waveforms')
+    arrs = []
+    for i, w in enumerate(waves):
+        a = np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError('tempo_gain_tables: waveform %d is not one-dimensional (shape %s)' % (i, a.shape))
+        arrs.append(a)
+    K = len(arrs)
+    tempo = np.ascontiguousarray(tempo, dtype=np.float64)
+    gain_db = np.ascontiguousarray(gain_db, dtype=np.float32)
+    if tempo.shape != (K,) or gain_db.shape != (K,):
+        raise ValueError('tempo_gain_tables: %s tempo factors and %s gains for %d waveforms' % (tempo.shape, gain_db.shape, K))
+    S, R, O = wsola_geometry(sample_rate)
+    if R + 1 > 256 or O > 256:
+        raise ValueError('tempo_gain_tables: a search of %d or an overlap of %d samples (sample rate %s) is beyond the 256 the kernel covers'
+                         % (R, O, sample_rate))
+    H = S - O
+    lengths = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+    out_lengths = np.array([TempoGainAugment.out_length(n, t) for n, t in zip(lengths, tempo)], dtype=np.int64)
+    offsets, out_offsets, seg_base = (np.zeros(K + 1, dtype=np.int64) for _ in range(3))
+    np.cumsum(lengths, out=offsets[1:])
+    np.cumsum(out_lengths, out=out_offsets[1:])
+    np.cumsum(np.where(tempo == 1.0, 0, (out_lengths + H - 1) // H), out=seg_base[1:])
+    gain = (10.0 ** (gain_db.astype(np.float64) / 20.0)).astype(np.float32)
+    return dict(flat=np.concatenate(arrs), offsets=offsets, out_offsets=out_offsets, seg_base=seg_base, tempo=tempo, gain=gain,
+                geometry=(S, R, O))
+
+
+def _tempo_gain_launch(lib, stream, tab, d_wav, d_off, d_ooff, d_sbase, d_tempo, d_gain, quantize, device):
+    """mtl_tempo_search, then mtl_tempo_render on `stream` (operands on the device, output allocated with the current stream) ->
+    (stretched packed waveforms float32, seg_off int32)"""
+    from . import _lib
+    K, (S, R, O) = tab['tempo'].shape[0], tab['geometry']
+    out = torch.empty(max(int(tab['out_offsets'][-1]), 1), dtype=torch.float32, device=device)
+    seg_off = torch.empty(max(int(tab['seg_base'][-1]), 1), dtype=torch.int32, device=device)
+    _lib.check(lib.mtl_tempo_search(stream, d_wav.data_ptr(), d_off.data_ptr(), d_ooff.data_ptr(), d_tempo.data_ptr(), d_sbase.data_ptr(), K,
+                                    S, R, O, seg_off.data_ptr()), 'mtl_tempo_search')
+    _lib.check(lib.mtl_tempo_render(stream, d_wav.data_ptr(), d_off.data_ptr(), d_ooff.data_ptr(), d_tempo.data_ptr(), d_gain.data_ptr(),
+                                    d_sbase.data_ptr(), seg_off.data_ptr(), K, S, R, O, 1 if quantize else 0, out.data_ptr()),
+               'mtl_tempo_render')
+    return out[:int(tab['out_offsets'][-1])], seg_off[:int(tab['seg_base'][-1])]
+
+
+def tempo_gain(waves, tempo, gain_db, sample_rate=16000, quantize=True, device='cuda'):
+    """K waveforms stretched to tempo[k] and amplified by gain_db[k] on the device (TempoGainAugment for the semantics) ->
+    (list of K float32 numpy arrays, seg_off int32 numpy: the offsets o_m of all segments, utterance after utterance; an utterance at
+    tempo 1.0 has none).  quantize=False leaves out gain and the 16-bit rounding: the raw overlap-add.  The unfused form of
+    `SpectrogramFrontEnd.batch(augment=)`, on the current stream."""
+    from . import _lib
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('tempo and gain are applied on the MI355X only (no CPU fallback)')
+    tab = tempo_gain_tables(waves, tempo, gain_db, sample_rate)
+    lib = _lib.lib()
+    d = {k: torch.from_numpy(tab[k]).to(dev) for k in ('flat', 'offsets', 'out_offsets', 'seg_base', 'tempo', 'gain')}
+    if d['flat'].numel() == 0:
+        d['flat'] = torch.zeros(1, device=dev)
+    out, seg_off = _tempo_gain_launch(lib, torch.cuda.current_stream(dev).cuda_stream, tab, d['flat'], d['offsets'], d['out_offsets'],
+                                      d['seg_base'], d['tempo'], d['gain'], quantize, dev)
+    out, oo = out.cpu().numpy(), tab['out_offsets']
+    return [out[oo[k]:oo[k + 1]].copy() for k in range(len(waves))], seg_off.cpu().numpy()
+
+
+def load_randomly_augmented_audio(path, sample_rate=16000, tempo_range=(0.85, 1.15), gain_range=(-6, 8)):
+    """utils/audio.py:50-61 on the device: tempo and gain drawn from the global np.random like the reference, the utterance as float32
+    numpy (16-bit PCM at `sample_rate`: no resampling here)"""
+    tempo, gain_db = TempoGainAugment(tempo_range, gain_range).draw(np.random)
+    return tempo_gain([load_wav_pcm16(path)], [tempo], [gain_db], sample_rate)[0][0]
+
+
 class SpectrogramFrontEnd:
     """wav -> STFT (n_fft = win = sample_rate*window_size, hop = sample_rate*window_stride, symmetric Hamming window,
     center + reflect padding = librosa.stft defaults of the reference era) -> |.| -> log1p -> (x-mean)/std, all on the MI355X:
@@ -460,6 +623,7 @@ class SpectrogramFrontEnd:
         """consumer: the stream on which the batches of `batch()` are read (default: the device's current stream at construction --
         the stream on which TransientTrainer._batched_iteration copies device-resident inputs into its static buffers)."""
         from scipy.signal import windows as sw
+        self.sample_rate = sample_rate
         self.n_fft = int(sample_rate * window_size)
         self.hop = int(sample_rate * window_stride)
         self.F = self.n_fft // 2 + 1
@@ -480,6 +644,7 @@ class SpectrogramFrontEnd:
         self.stream = None                                     # batch()'s own stream, made at its first call
         self._pin_wav = self._pin_off = None                   # pinned staging of batch(), grown on demand
         self._pin_noff = self._pin_lvl = None                  # ... and of its two noise tables
+        self._pin_aug = self._pin_tempo = self._pin_gain = None # ... and of the augmentation tables
 
     def __call__(self, y):
         """y: 1-D float waveform (numpy or tensor) -> (F, T) fp32 tensor on the device, T = 1 + len(y) // hop."""
@@ -500,7 +665,7 @@ class SpectrogramFrontEnd:
                                         1 if self.normalize else 0), 'mtl_spect_logmag')
         return out
 
-    def batch(self, waves, max_frames=None, noise=None):
+    def batch(self, waves, max_frames=None, noise=None, augment=None):
         """K waveforms -> (inputs (K, 1, F, Tmax) fp32 on the device, input_sizes (K) int32 on the host): what `collate` builds from
         K `__call__` results cut to max_frames, in one device pass -- one pinned staging copy of the concatenated samples and of the
         offsets (two H2D copies) and the two launches of mtl_spect_batch (framing, STFT, log-magnitude, per-utterance statistics over
@@ -519,12 +684,35 @@ class SpectrogramFrontEnd:
         level[k], as NoiseInjection.inject_noise_sample does (utils/data_loader.py:383-399), while the samples are staged -- no mixed
         waveform exists in memory and the host does not touch the samples.  The two tables (K int64, K float32) travel through
         pinned staging like the offsets; the calls are mtl_wave_mix_coef, then mtl_spect_batch_noise, on the same stream under the
-        same event.  noise=None issues exactly the calls described above."""
+        same event.  noise=None issues exactly the calls described above.
+
+        augment=(tempo, gain_db), K values each (`TempoGainAugment.plan` for these K waveforms): utterance k is first stretched to
+        tempo[k] and amplified by gain_db[k] as `tempo_gain` does -- mtl_tempo_search, then mtl_tempo_render into a packed buffer of the
+        stretched waveforms at new offsets -- and the calls above run unchanged on THAT buffer and its offsets, all on the same stream
+        under the same event: the result is bitwise `batch(tempo_gain(waves, tempo, gain_db)[0], ...)`.  input_sizes, Tmax and the
+        n_fft // 2 + 1 minimum of `pack_waveforms` refer to the stretched lengths, and a noise plan must have been made for them.  The
+        offsets, the segment table's prefix, the factors and the gains travel through pinned staging like the noise tables.
+        augment=None issues exactly the calls described above."""
         from . import _lib
         if self.device.type != 'cuda':
             raise RuntimeError('the spectrogram front-end runs on the MI355X only (no CPU fallback)')
         lib = _lib.lib()
-        flat, offsets, frames, tmax = pack_waveforms(waves, self.hop, self.n_fft, max_frames)
+        aug = None
+        if augment is None:
+            flat, offsets, frames, tmax = pack_waveforms(waves, self.hop, self.n_fft, max_frames)
+        else:
+            # the samples that are uploaded are the original ones; everything downstream sees the stretched lengths
+            aug = tempo_gain_tables(waves, augment[0], augment[1], self.sample_rate)
+            flat, offsets = aug['flat'], aug['out_offsets']
+            short = np.flatnonzero(np.diff(offsets) < self.n_fft // 2 + 1)
+            if short.size:
+                raise ValueError('batch: utterance %d has %d samples after the tempo change, fewer than n_fft // 2 + 1 = %d (one reflection '
+                                 'must suffice)' % (short[0], np.diff(offsets)[short[0]], self.n_fft // 2 + 1))
+            frames = 1 + np.diff(offsets) // self.hop
+            if max_frames is not None:
+                frames = np.minimum(frames, max_frames)
+            frames = frames.astype(np.int32)
+            tmax = int(frames.max())
         K = len(frames)
         total_frames = int((1 + np.diff(offsets) // self.hop).sum())
         ws_bytes = lib.mtl_spect_batch_workspace(total_frames, K, self.F)
@@ -556,6 +744,15 @@ class SpectrogramFrontEnd:
                 self._pin_lvl = torch.empty(max(K, 64), dtype=torch.float32).pin_memory()
             self._pin_noff[:K].copy_(torch.from_numpy(noise_off))
             self._pin_lvl[:K].copy_(torch.from_numpy(level))
+        if aug is not None:
+            if self._pin_aug is None or self._pin_aug.numel() < 2 * (K + 1):
+                self._pin_aug = torch.empty(max(2 * (K + 1), 128), dtype=torch.int64).pin_memory()
+                self._pin_tempo = torch.empty(max(K, 64), dtype=torch.float64).pin_memory()
+                self._pin_gain = torch.empty(max(K, 64), dtype=torch.float32).pin_memory()
+            self._pin_aug[:K + 1].copy_(torch.from_numpy(aug['offsets']))
+            self._pin_aug[K + 1:2 * (K + 1)].copy_(torch.from_numpy(aug['seg_base']))
+            self._pin_tempo[:K].copy_(torch.from_numpy(aug['tempo']))
+            self._pin_gain[:K].copy_(torch.from_numpy(aug['gain']))
         with torch.cuda.stream(self.stream):
             inputs = torch.empty(K, 1, self.F, tmax, device=self.device)
             d_wav = torch.empty(flat.shape[0], device=self.device)
@@ -563,6 +760,15 @@ class SpectrogramFrontEnd:
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
             d_wav.copy_(self._pin_wav[:flat.shape[0]], non_blocking=True)
             d_off.copy_(self._pin_off[:K + 1], non_blocking=True)
+            if aug is not None:                                 # d_wav holds the original samples, d_off the STRETCHED offsets
+                d_aug = torch.empty(2 * (K + 1), dtype=torch.int64, device=self.device)
+                d_tempo = torch.empty(K, dtype=torch.float64, device=self.device)
+                d_gain = torch.empty(K, dtype=torch.float32, device=self.device)
+                d_aug.copy_(self._pin_aug[:2 * (K + 1)], non_blocking=True)
+                d_tempo.copy_(self._pin_tempo[:K], non_blocking=True)
+                d_gain.copy_(self._pin_gain[:K], non_blocking=True)
+                d_wav, _ = _tempo_gain_launch(lib, self.stream.cuda_stream, aug, d_wav, d_aug[:K + 1], d_off, d_aug[K + 1:], d_tempo, d_gain,
+                                              True, self.device)
             if noise is None:
                 _lib.check(lib.mtl_spect_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
                                                self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax, 1 if self.normalize else 0,
@@ -586,6 +792,11 @@ class SpectrogramFrontEnd:
         done.synchronize()                                     # host wait on this stream's event only
         inputs.record_stream(self.consumer)
         return inputs, torch.from_numpy(frames)
+
+
+    def tempo_gain(self, waves, tempo, gain_db, quantize=True):
+        """`tempo_gain` at this front-end's sample rate and device: (list of K stretched float32 numpy arrays, seg_off)"""
+        return tempo_gain(waves, tempo, gain_db, self.sample_rate, quantize, self.device)
 
 
 class NoiseInjection(object):

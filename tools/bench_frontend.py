@@ -23,6 +23,16 @@ over a seeded noise corpus of four 30-second files written to a temporary direct
 mtl_spect_batch_noise and mtl_wave_mix_coef alone.
 
     python tools/bench_frontend.py --noise-out profiles/frontend_noise.json
+
+--augment [--augment-out PATH] runs the tempo / gain leg instead, same protocol, three paths that alternate:
+
+  (a) clean:         `batch(waves)`
+  (b) per utterance: K x `__call__(y).cpu()`, `collate`, `.to(device)`  (the figure an augmented batch must stay under to be worth it)
+  (c) augmented:     `batch(waves, augment=(tempo, gain_db))`, every utterance stretched (seeded draws of TempoGainAugment)
+
+plus the HIP-event times of mtl_tempo_search, mtl_tempo_render and of mtl_spect_batch on the stretched buffer alone.
+
+    python tools/bench_frontend.py --augment --augment-out profiles/frontend_augment.json
 """
 import argparse
 import json
@@ -53,6 +63,8 @@ def main():
     ap.add_argument('--queued-ms', type=float, default=100.0)
     ap.add_argument('--out', default=None)
     ap.add_argument('--noise-out', default=None)
+    ap.add_argument('--augment', action='store_true')
+    ap.add_argument('--augment-out', default=None)
     a = ap.parse_args()
     if a.reps < 20 or a.warmup < 3:
         ap.error('at least 20 timed calls after at least 3 warm-ups')
@@ -66,6 +78,8 @@ def main():
     dev = fe.device
     if a.noise_out:
         return noise_leg(a, mtl_amd, _lib, fe, waves)
+    if a.augment or a.augment_out:
+        return augment_leg(a, mtl_amd, _lib, fe, waves, labels)
 
     def per_utterance():
         specs = [fe(y).cpu() for y in waves]
@@ -262,6 +276,112 @@ def noise_leg(a, mtl_amd, _lib, fe, waves):
     with open(a.noise_out, 'w') as f:
         json.dump(res, f, indent=1, sort_keys=True)
         f.write('\n')
+
+
+def augment_leg(a, mtl_amd, _lib, fe, waves, labels):
+    K, dev = len(waves), fe.device
+    waves = [(np.rint(y.astype(np.float64) * 32768.0) / 32768.0).astype(np.float32) for y in waves]      # what a 16-bit file holds
+    aug, rng = mtl_amd.TempoGainAugment(), np.random.RandomState(1)
+    tempo, gain_db, out_lengths = aug.plan([aug.draw(rng) for _ in range(K)], [len(y) for y in waves])
+    assert (tempo != 1.0).all()
+
+    def clean():
+        return fe.batch(waves)[0]
+
+    def per_utterance():
+        specs = [fe(y).cpu() for y in waves]
+        return mtl_amd.data.collate(specs, labels)[0].to(dev)
+
+    def augmented():
+        return fe.batch(waves, augment=(tempo, gain_db))[0]
+
+    # the augmented batch must be the batch of the unfused form's waveforms before its time means anything
+    stretched, seg_off = fe.tempo_gain(waves, tempo, gain_db)
+    xa, xc = fe.batch(stretched)[0], augmented()
+    torch.cuda.synchronize()
+    assert [len(s) for s in stretched] == out_lengths.tolist() and torch.equal(xa, xc)
+
+    m = torch.randn(4096, 4096, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        m @ m
+    e0.record()
+    for _ in range(20):
+        m @ m
+    e1.record()
+    torch.cuda.synchronize()
+    chain = max(int(round(a.queued_ms / (e0.elapsed_time(e1) / 20))), 1)
+
+    def timed(fn, busy):
+        torch.cuda.synchronize()
+        if busy:
+            for _ in range(chain):
+                m @ m
+        t0 = time.perf_counter()
+        x = fn()
+        dt = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        del x
+        return dt
+
+    paths = (('clean', clean), ('per_utterance', per_utterance), ('augmented', augmented))
+    times = {(name, busy): [] for name, _ in paths for busy in (False, True)}
+    for rep in range(a.warmup + a.reps):
+        for busy in (False, True):
+            for name, fn in paths:
+                dt = timed(fn, busy)
+                if rep >= a.warmup:
+                    times[(name, busy)].append(dt)
+
+    # device time of the launches alone (operands on the device)
+    lib = _lib.lib()
+    tab = mtl_amd.tempo_gain_tables(waves, tempo, gain_db, 16000)
+    S, R, O = tab['geometry']
+    d = {k: torch.from_numpy(tab[k]).to(dev) for k in ('flat', 'offsets', 'out_offsets', 'seg_base', 'tempo', 'gain')}
+    seg = torch.empty(int(tab['seg_base'][-1]), dtype=torch.int32, device=dev)
+    d_str = torch.empty(int(tab['out_offsets'][-1]), device=dev)
+    frames = 1 + np.diff(tab['out_offsets']) // fe.hop
+    tmax = int(frames.max())
+    out = torch.empty(K, 1, fe.F, tmax, device=dev)
+    ws_bytes = lib.mtl_spect_batch_workspace(int(frames.sum()), K, fe.F)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    head = (st, d['flat'].data_ptr(), d['offsets'].data_ptr(), d['out_offsets'].data_ptr(), d['tempo'].data_ptr())
+    calls = dict(
+        tempo_search=lambda: lib.mtl_tempo_search(*(head + (d['seg_base'].data_ptr(), K, S, R, O, seg.data_ptr()))),
+        tempo_render=lambda: lib.mtl_tempo_render(*(head + (d['gain'].data_ptr(), d['seg_base'].data_ptr(), seg.data_ptr(), K, S, R, O, 1,
+                                                            d_str.data_ptr()))),
+        spect_batch=lambda: lib.mtl_spect_batch(st, d_str.data_ptr(), d['out_offsets'].data_ptr(), K, fe.n_fft, fe.hop, fe.basis.data_ptr(),
+                                                fe.ldb, fe.F, out.data_ptr(), tmax, 1, ws.data_ptr(), ws_bytes))
+    launch_us = {name: [] for name in calls}
+    for rep in range(a.warmup + a.reps):
+        for name in ('tempo_search', 'tempo_render', 'spect_batch'):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(calls[name](), name)
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                launch_us[name].append(1e3 * e0.elapsed_time(e1))
+    assert torch.equal(seg.cpu(), torch.from_numpy(seg_off))
+
+    key = lambda n, b: '%s_%s' % (n, 'busy' if b else 'idle')
+    segments = np.diff(tab['seg_base'])
+    res = dict(device=torch.cuda.get_device_name(0), utterances=K, samples_per_utterance=a.samples, reps=a.reps, warmup=a.warmup,
+               queued_ms=a.queued_ms, queued_products=chain, tempo_min_max=[float(tempo.min()), float(tempo.max())],
+               stretched_samples_min_max=[int(out_lengths.min()), int(out_lengths.max())],
+               segments_per_utterance_min_max=[int(segments.min()), int(segments.max())],
+               utt_per_s={key(n, b): K / statistics.median(v) for (n, b), v in times.items()},
+               call_ms_median={key(n, b): 1e3 * statistics.median(v) for (n, b), v in times.items()},
+               call_ms_min_max={key(n, b): [1e3 * min(v), 1e3 * max(v)] for (n, b), v in times.items()},
+               launches_us_median={n: statistics.median(v) for n, v in launch_us.items()},
+               launches_us_min={n: min(v) for n, v in launch_us.items()},
+               search_us_per_link=statistics.median(launch_us['tempo_search']) / max(int(segments.max()) - 1, 1))
+    print(json.dumps(res))
+    if a.augment_out:
+        with open(a.augment_out, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write('\n')
 
 
 if __name__ == '__main__':
