@@ -452,6 +452,39 @@ int mtl_tempo_search(void* stream, const float* wav, const long* offsets, const 
 int mtl_tempo_render(void* stream, const float* wav, const long* offsets, const long* out_offsets, const double* tempo, const float* gain,
                      const long* seg_base, const int* seg_off, int K, int seg, int search, int overlap, int quantize, float* out);
 
+/* ---- accent discriminator on the encoder output (joint_train.py --multitask / --adversarial) ------------------------------
+ * modules/discriminator.py, trainer/asr/joint_trainer.py:29-37, utils/metrics.py:164-199 (csrc/mtl_disc.hip):
+ *   pooled[b][:] = sum_t enc[b][t][:]                      all T rows: the encoder leaves the rows beyond an utterance's length at zero
+ *   logits[b][c] = pooled[b] . W[c] + bias[c]              Discriminator.linear, W (C, d), bias (C)
+ *   losses[0]    = mean_b ( logsumexp(logits[b]) - logits[b][accent_id] )          F.cross_entropy(logits, [accent_id] * B)
+ *   losses[1]    = mean_{b,c} ( logits[b][c] - 1/C )^2                              F.mse_loss(logits, 1/C), mode 1 only
+ * mode 0 = multi-task (CE only), 1 = adversarial (CE and MSE).
+ * mtl_disc_fwd: enc is (B T, d), rows in (b, t) order.  The time sum is a two-stage reduction in a fixed order, no atomics: stage 1,
+ *   workgroups over (b, chunk of MTL_DISC_CHUNK rows), writes per-chunk column sums into `workspace` with 16-byte loads along d;
+ *   stage 2 adds an utterance's partials in chunk order and forms its logits; a third launch forms the losses.  pooled (B, d) and
+ *   logits (B, C) are outputs, kept by the caller for the backward.
+ * mtl_disc_bwd, for the loss  a losses[0] + b losses[1]  (b counts in mode 1 only):
+ *   dlogit[b][c]  = a (softmax(logits[b])[c] - [c == accent_id]) / B + b 2 (logits[b][c] - 1/C) / (B C)
+ *   dW[c][:]     += sum_b dlogit[b][c] pooled[b][:] ,  dbias[c] += sum_b dlogit[b][c]                    (both in batch order)
+ *   denc[b][t][:] += sum_c dlogit[b][c] W[c][:]   for every t < T     (one read-modify-write of denc, 16 bytes per lane)
+ * mtl_disc_loss_fwd / mtl_disc_loss_bwd: the loss half alone on given logits (B, C) -- the launches the two calls above end / begin
+ *   with; the backward WRITES dlogits (calculate_adversarial / calculate_multi_task on arbitrary logits).
+ * mtl_disc_bwd_dlogits: the three accumulations of mtl_disc_bwd for a GIVEN dlogit (B, C) (the gradient autograd hands to the logits).
+ * Limits: 1 <= C <= 64, 0 <= accent_id < C, d % 4 == 0, 1 <= B <= 65535, T >= 1, enc / denc / W / workspace 16-byte aligned,
+ *   ws_bytes >= mtl_disc_workspace(B, T, d); anything else returns -22 before any launch. */
+#ifndef MTL_DISC_CHUNK
+#define MTL_DISC_CHUNK 16   /* rows of one utterance per stage-1 workgroup */
+#endif
+long mtl_disc_workspace(int B, int T, int d);
+int mtl_disc_fwd(void* stream, const float* enc, int B, int T, int d, const float* W, const float* bias, int C, int accent_id, int mode,
+                 float* pooled, float* logits, float* losses, float* workspace, long ws_bytes);
+int mtl_disc_bwd(void* stream, const float* pooled, const float* logits, const float* W, int accent_id, int B, int T, int d, int C, int mode,
+                 float a, float b, float* dW, float* dbias, float* denc);
+int mtl_disc_bwd_dlogits(void* stream, const float* pooled, const float* dlogits, const float* W, int B, int T, int d, int C, float* dW,
+                         float* dbias, float* denc);
+int mtl_disc_loss_fwd(void* stream, const float* logits, int B, int C, int accent_id, int mode, float* losses);
+int mtl_disc_loss_bwd(void* stream, const float* logits, int B, int C, int accent_id, int mode, float a, float b, float* dlogits);
+
 /* ---- LSTM cell, one time step (lm/model/rnn_model.py:20 nn.LSTM; lm/main_meta_transfer.py:277-411) ----------
  * gx = x_t . W_ih^T + b_ih and gh = h_{t-1} . W_hh^T + b_hh come from mtl_gemm_f32_ex (B x 4H each, torch gate order i|f|g|o).
  * forward: acts = activated gates (saved), c = f*c_prev + i*g, h = o*tanh(c); h_drop (nullable) = h [* mask * mscale]: the

@@ -8,6 +8,8 @@ from .data import (Vocab, SyntheticTask, ManifestTaskDataset, SpectrogramDataset
                    synth_batch, is_chinese_char, is_contain_chinese_word, get_word_segments_per_language)
 from .functions import (init_transformer_model, save_meta_model, load_meta_model, save_joint_model, load_joint_model,  # noqa: F401
                         post_process, compute_num_params)
+from .discriminator import (Discriminator, init_discriminator_model, save_discriminator, load_discriminator,  # noqa: F401
+                            calculate_adversarial, calculate_multi_task)
 from .metrics import calculate_metrics, calculate_cer, calculate_wer, calculate_cer_en_zh  # noqa: F401
 from .model import Transformer, Encoder, Decoder  # noqa: F401
 from .trainer import TransientTrainer, JointTrainer, FlatAdam, FlatSGD  # noqa: F401

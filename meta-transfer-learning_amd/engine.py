@@ -1758,15 +1758,33 @@ class PassEngine:
         host = state.cpu().numpy()                                # (synchronises: the one read-back of the chunk)
         return beam_unpack(host, Uc, W, npos, start_token, eos_id)
 
-    def backward(self, grad, scale=1.0, dpred=None, sG=0):
+    def encoder_output(self):
+        """(B, T', d) view of the LAST forward's encoder memory (what the decoder attends to; `backward` calls it mem_ptr).  T' is the
+        pass's own extent (a widened stand-alone pass carries more positions than the batch); rows at and beyond an utterance's
+        length are zero.  Valid until the next forward of this engine."""
+        S = self.saved
+        if S is None:
+            raise RuntimeError('encoder_output() without a preceding forward()')
+        if S['nt'] != 1:
+            raise ValueError('encoder_output() is defined for single-task passes')
+        hp = self.hp
+        mem = self.arena['e%d.ff.y' % (hp.n_enc - 1)] if hp.n_enc else self.arena['enc_in.y']
+        return mem.view(S['B'], (S['T'] // 2) // 2, hp.d)
+
+    def backward(self, grad, scale=1.0, dpred=None, sG=0, dmem_hook=None):
         """Accumulate `scale` * dLoss/dtheta of the LAST forward into the flat buffer `grad` (+=).
         dpred: optional externally supplied gradient w.r.t. pred (B,Td,V) instead of the fused CE backward.
-        Task-batched pass: task t accumulates into grad + t * sG floats (sG = layout.total: a stack of per-task gradients)."""
+        Task-batched pass: task t accumulates into grad + t * sG floats (sG = layout.total: a stack of per-task gradients).
+        dmem_hook: called with the (B * T', d) gradient of the encoder output once the decoder has completed it and before the
+        encoder's backward reads it, on the pass's main stream: a further head on encoder_output() adds its gradient there
+        (single-task passes only)."""
         S = self.saved
         if S is None:
             raise RuntimeError('backward() without a preceding forward()')
         hp, L, lib, st, A = self.hp, self.L, self.lib, self.stream, self.arena
         nt = S['nt']
+        if dmem_hook is not None and nt > 1:
+            raise ValueError('dmem_hook: a gradient enters at the encoder output of single-task passes only')
         self.nt, self.sP, self.sG = nt, S['sP'], int(sG) if nt > 1 else 0
         if nt > 1 and (sG != L.total or grad.numel() != nt * L.total or dpred is not None):
             raise ValueError('a task-batched backward accumulates into a (tasks, layout.total) gradient stack')
@@ -1852,6 +1870,8 @@ class PassEngine:
                 self.flush_ln_reduce()
             self._slice_done('decoder')
 
+        if dmem_hook is not None:
+            dmem_hook(dmem)
         # ---- encoder ----
         eA = self.buf('_deA', (nt * Me, d))
         dcur, dnext = dmem, eA

@@ -138,6 +138,31 @@ class _ModelFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class _ModelEncFn(torch.autograd.Function):
+    """(pred, gold, hyp, enc_output) = model(x, lengths, target): _ModelFn with the encoder output (B, T', d) as a fourth,
+    differentiable output; its incoming gradient joins the encoder-output gradient inside the engine's backward (dmem_hook)."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, x, lengths, target):
+        out = model._run_forward(model._theta_for_forward(), x, lengths, target)
+        ctx.model = model
+        ctx.token = model._pass_token
+        pred, gold, hyp = (out[k].view(out[k].shape) for k in ('pred', 'gold', 'hyp'))
+        enc = model.engine.encoder_output()
+        ctx.mark_non_differentiable(gold, hyp)
+        return pred, gold, hyp, enc.view(enc.shape)
+
+    @staticmethod
+    def backward(ctx, dpred, _g, _h, denc):
+        m = ctx.model
+        if ctx.token != m._pass_token:
+            raise RuntimeError('backward through a stale forward: the engine keeps the activations of the last forward only')
+        m._sync_grad_views()
+        denc = denc.contiguous().float()
+        m.engine.backward(m._gflat, 1.0, dpred=dpred, dmem_hook=lambda dmem: m._axpy(dmem, denc, 1.0))
+        return None, None, None, None, None
+
+
 class Transformer(nn.Module):
     def __init__(self, encoder, decoder, vocab, feat_extractor='vgg_cnn', train=True, is_factorized=False, r=100):
         super().__init__()
@@ -258,6 +283,11 @@ class Transformer(nn.Module):
         Same contract as models/asr/transformer.py:120-149."""
         return _ModelFn.apply(self._anchor, self, padded_input, input_lengths, padded_target)
 
+    def forward_with_encoder_output(self, padded_input, input_lengths, padded_target):
+        """forward() plus the encoder output (B, T', d) as a differentiable fourth result: what a head on the encoder output (the
+        accent discriminator) reads; both results come from ONE pass of the engine."""
+        return _ModelEncFn.apply(self._anchor, self, padded_input, input_lengths, padded_target)
+
     # fast path used by the trainer: no autograd objects at all
     def pass_forward(self, x, lengths, target, theta=None, smoothing=0.0, lane=0):
         if lane == 0:
@@ -268,9 +298,9 @@ class Transformer(nn.Module):
             x = x.to(th.device, non_blocking=True)
         return self.engines[lane].forward(th, x.float(), lengths, target, smoothing=smoothing)
 
-    def pass_backward(self, grad=None, scale=1.0, lane=0):
+    def pass_backward(self, grad=None, scale=1.0, lane=0, dmem_hook=None):
         self._need_engine()
-        self.engines[lane].backward(self._gflat if grad is None else grad, scale)
+        self.engines[lane].backward(self._gflat if grad is None else grad, scale, dmem_hook=dmem_hook)
 
     # ------------------------------------------------------------------ copy_grad API (models/asr/transformer.py:205-240)
     def init_copy_grad_(self):

@@ -22,6 +22,7 @@ import torch
 
 from . import _lib, _trace, dist as mdist, hostenv
 from .engine import CENSUS_NAMES, CENSUS_SLOTS, PAD_ID, round_width
+from .discriminator import calculate_adversarial, calculate_multi_task, save_discriminator
 from .functions import post_process, save_joint_model, save_meta_model
 from .metrics import calculate_cer, calculate_metrics
 
@@ -209,15 +210,26 @@ def cer_counts(vocab, gold, hyp):
     return total_cer, total_char
 
 
-def sync_replicas_from_rank0(model, opts):
+def sync_replicas_from_rank0(model, opts, discriminator=None):
     """Multi-rank start-up: broadcast theta and every optimizer's state (Adam m, v, step count) from rank 0, so that replicas are
     bit-identical whatever each rank's RNG / checkpoint state was.  From then on they stay identical by construction (same G
-    after the all-reduce, deterministic Adam kernel); check_replicas() verifies that periodically."""
+    after the all-reduce, deterministic Adam kernel); check_replicas() verifies that periodically.
+    discriminator: its flat parameters join; a torch.optim optimizer among `opts` (opt_disc) sends whatever state tensors it holds
+    (none when it was built for this train() call, on every rank alike)."""
     if mdist.world_size() <= 1:
         return
     import torch.distributed as td
     td.broadcast(model.flat_parameters, src=0)
+    if discriminator is not None:
+        td.broadcast(discriminator.flat_parameters, src=0)
     for opt in opts:
+        if isinstance(opt, torch.optim.Optimizer):
+            for group in opt.param_groups:
+                for p in group['params']:
+                    for k in sorted(k for k, v in opt.state.get(p, {}).items() if torch.is_tensor(v)):
+                        v = opt.state[p][k].to(model.flat_parameters.device)
+                        td.broadcast(v, src=0)
+                        opt.state[p][k].copy_(v)
         if isinstance(opt, FlatAdam):
             td.broadcast(opt.m, src=0)
             td.broadcast(opt.v, src=0)
@@ -1075,29 +1087,91 @@ class TransientTrainer():
 
 class JointTrainer():
     """Drop-in for trainer/asr/joint_trainer.py (BASELINE.json configs[0], joint_train.py): per iteration the gradient of
-    sum_m L_tr,m / n over all tasks, optional clip, ONE Adam(lr=args.lr) step (joint_trainer.py:182-262, no discriminator).
+    sum_m L_tr,m / n over all tasks, optional clip, ONE Adam(lr=args.lr) step (joint_trainer.py:182-262).
+    With a discriminator (--multitask / --adversarial [--beta-decay], joint_trainer.py:208-256) task m adds w CE(accent = m) / n
+    [+ MSE(logits, 1/C) / n] of the accent head on its encoder output; the head's own Adam(lr=args.lr_disc) steps after the model's.
     Same engine and kernels as the meta loop; tasks shard over ranks the same way."""
+
+    BETA_DECAY = 0.99997                                                # joint_trainer.py:156
 
     def __init__(self):
         logging.info('Joint Trainer is initialized')
+        self.beta = 1.0                                                 # joint_trainer.py:155: carried across iterations
 
     def get_lr(self, optimizer):
         return optimizer.param_groups[0]['lr']
 
-    def run_iteration(self, model, vocab, task_batches, n_tasks, opt, args):
+    def forward_one_batch(self, model, vocab, src, trg, src_percentages, src_lengths, trg_lengths, smoothing, loss_type, verbose=False,
+                          discriminator=None, accent_id=None, multi_task=False):
+        """joint_trainer.py:25-91 -> (loss, total_cer, total_char) | (..., disc_loss) with multi_task | (..., disc_loss, enc_loss):
+        differentiable tensors, one backward through their sum reaches the model and the discriminator."""
+        if discriminator is None:
+            return TransientTrainer.forward_one_batch(self, model, vocab, src, trg, src_percentages, src_lengths, trg_lengths, smoothing,
+                                                      loss_type, verbose=verbose)
+        if loss_type != 'ce':
+            raise NotImplementedError("only loss_type='ce' is on the accelerated path")
+        pred, gold, hyp, enc_output = model.forward_with_encoder_output(src, src_lengths, trg)
+        accent_pred = discriminator(enc_output)                         # discriminator(torch.sum(enc_output, dim=1))
+        if multi_task:
+            disc_loss = calculate_multi_task(accent_pred, accent_id)
+        else:
+            disc_loss, enc_loss = calculate_adversarial(accent_pred, accent_id)
+        sizes = src_percentages.mul_(int(pred.size(1))).int()
+        loss, _ = calculate_metrics(pred, gold, vocab.PAD_ID, input_lengths=sizes, target_lengths=trg_lengths, smoothing=smoothing,
+                                    loss_type=loss_type)
+        total_cer, total_char = cer_counts(vocab, gold.cpu(), hyp.cpu())
+        if verbose:
+            print('Total CER', total_cer)
+            print('Total char', total_char)
+        if multi_task:
+            return loss, total_cer, total_char, disc_loss
+        return loss, total_cer, total_char, disc_loss, enc_loss
+
+    def run_iteration(self, model, vocab, task_batches, n_tasks, opt, args, discriminator=None, opt_disc=None, task_ids=None):
+        """One iteration over this rank's task batches.  discriminator / opt_disc: the accent head and its optimizer; task_ids: the
+        tasks' indices among all n_tasks (their accent ids; default 0, 1, ...).  -> [total_loss, total_cer, total_char] and, with a
+        discriminator, total_disc_loss (weighted, as logged) and total_enc_loss."""
         dev = model.flat_parameters.device
         g = model.flat_grad
         smoothing = float(getattr(args, 'label_smoothing', 0.0) or 0.0)
         g.zero_()                                                       # opt.zero_grad()
         reads = []
-        for (tx, tsz, _tp, ty, _tl) in task_batches:
-            out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing)
-            reads.append(_Readback(out, ('joint', len(reads), 0)))
-            model.pass_backward(g, 1.0 / n_tasks)                       # (tr_loss / n).backward()
+        if discriminator is None:
+            for (tx, tsz, _tp, ty, _tl) in task_batches:
+                out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing)
+                reads.append(_Readback(out, ('joint', len(reads), 0)))
+                model.pass_backward(g, 1.0 / n_tasks)                   # (tr_loss / n).backward()
+        else:
+            adversarial = bool(getattr(args, 'adversarial', False))
+            decay = adversarial and bool(getattr(args, 'beta_decay', False))
+            task_ids = list(range(len(task_batches))) if task_ids is None else list(task_ids)
+            batch_of = dict(zip(task_ids, task_batches))
+            discriminator.zero_grad()                                   # opt_disc.zero_grad()
+            weights, disc_reads = [], []
+            for m in range(n_tasks):                                    # beta decays at every task visit, whichever rank makes it
+                if decay:
+                    self.beta = self.beta * self.BETA_DECAY
+                if m not in batch_of:
+                    continue
+                w = 1.0 if not adversarial else (self.beta if decay else 0.5)
+                tx, tsz, _tp, ty, _tl = batch_of[m]
+                out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing)
+                reads.append(_Readback(out, ('joint', len(reads), 0)))
+                losses = discriminator.head_forward(model.engine.encoder_output(), m, adversarial)
+                host = _pinned(('disc', len(disc_reads), 0), (2,), torch.float32)
+                host.copy_(losses, non_blocking=True)
+                disc_reads.append(host)
+                weights.append(w)
+                # (tr_loss / n + w disc_loss / n [+ enc_loss / n]).backward(): the head's gradient enters at the encoder output
+                model.pass_backward(g, 1.0 / n_tasks, dmem_hook=lambda dmem, w=w: discriminator.head_backward(
+                    w / n_tasks, 1.0 / n_tasks if adversarial else 0.0, dmem))
+            mdist.allreduce_sum_(discriminator.flat_grad)
         mdist.allreduce_sum_(g)
         if args.clip:
             clip_flat_grad_(model, g, args.max_norm)
         opt.step(g)
+        if discriminator is not None:
+            opt_disc.step()
         torch.cuda.synchronize(dev)
         total_loss, total_cer, total_char = 0.0, 0, 0
         for rd in reads:
@@ -1105,13 +1179,24 @@ class JointTrainer():
             total_cer += c
             total_char += n
             total_loss += float(rd.loss[0])
-        return mdist.allreduce_scalars([total_loss, total_cer, total_char], dev)
+        if discriminator is None:
+            return mdist.allreduce_scalars([total_loss, total_cer, total_char], dev)
+        # the reference logs the WEIGHTED discriminator loss, formed in fp32 (joint_trainer.py:230-236)
+        self.task_losses = [(float(rd.loss[0]), float(h[0]), float(h[1])) for rd, h in zip(reads, disc_reads)]
+        total_disc = sum(float(torch.tensor(w, dtype=torch.float32) * h[0]) for w, h in zip(weights, disc_reads))
+        total_enc = sum(float(h[1]) for h in disc_reads) if adversarial else 0.0
+        return mdist.allreduce_scalars([total_loss, total_cer, total_char, total_disc, total_enc], dev)
 
     def train(self, model, vocab, train_data_list, valid_loader_list, loss_type, start_it, num_it, args, evaluate_every=1000,
               window_size=100, last_summary_every=1000, last_metrics=None, early_stop=10, cpu_state_dict=False, is_copy_grad=False,
               opt_name='adam', discriminator=None):
-        if loss_type != 'ce' or discriminator is not None or opt_name != 'adam':
-            raise NotImplementedError("accelerated joint training: loss_type='ce', opt_name='adam', no discriminator")
+        if loss_type != 'ce' or opt_name != 'adam':
+            raise NotImplementedError("accelerated joint training: loss_type='ce', opt_name='adam'")
+        if discriminator is not None:
+            model._need_engine()
+        if discriminator is not None and discriminator.flat_parameters.device != model.flat_parameters.device:
+            raise RuntimeError('the discriminator lives on %s, the model on %s: the product path needs both on one MI355X (call '
+                               '.cuda())' % (discriminator.flat_parameters.device, model.flat_parameters.device))
         rank, world = mdist.rank(), mdist.world_size()
         if rank == 0:
             print('TRAIN')
@@ -1119,6 +1204,12 @@ class JointTrainer():
         model.train()
         opt = FlatAdam(model, args.lr)                                  # the reference builds a fresh Adam per train() call
         self.opt = opt
+        opt_disc = None
+        if discriminator is not None:                                   # joint_trainer.py:125-126, 155
+            opt_disc = torch.optim.Adam(discriminator.parameters(), lr=args.lr_disc)
+            self.beta = 1.0
+        self.opt_disc = opt_disc
+        adversarial = discriminator is not None and bool(getattr(args, 'adversarial', False))
         n_tasks = len(train_data_list)
         my_tasks = mdist.shard_tasks(n_tasks, rank, world)
         buf = [[] for _ in range(n_tasks)]
@@ -1140,7 +1231,7 @@ class JointTrainer():
         best_valid_val, count_stop, failures = 1000000000, 0, 0
         early_stop_criteria, early_stop_val = early_stop.split(',')[0], int(early_stop.split(',')[1])
         last_sum_loss, last_sum_cer, last_sum_char = deque(maxlen=window_size), deque(maxlen=window_size), deque(maxlen=window_size)
-        sync_replicas_from_rank0(model, [opt])
+        sync_replicas_from_rank0(model, [opt] if discriminator is None else [opt, opt_disc], discriminator=discriminator)
         fob = TransientTrainer.forward_one_batch.__get__(self)             # the two reference trainers share this method body
         while it < num_it:
             try:
@@ -1149,15 +1240,27 @@ class JointTrainer():
                 prefetch.start()
                 start_time = time.time()
                 popped = [buf[m].pop() for m in range(n_tasks)]
-                total_loss, total_cer, total_char = self.run_iteration(model, vocab, [popped[m][0] for m in my_tasks], n_tasks, opt,
-                                                                       args)
+                # (without a discriminator the call carries the six positional arguments it always has)
+                disc_kw = {} if discriminator is None else dict(discriminator=discriminator, opt_disc=opt_disc, task_ids=my_tasks)
+                totals = self.run_iteration(model, vocab, [popped[m][0] for m in my_tasks], n_tasks, opt, args, **disc_kw)
+                total_loss, total_cer, total_char = totals[:3]
+                total_disc_loss, total_enc_loss = totals[3:] if discriminator is not None else (None, None)
                 total_time += time.time() - start_time
                 self.loss_trace.append(total_loss / n_tasks)
                 last_sum_cer.append(total_cer)
                 last_sum_char.append(total_char)
                 last_sum_loss.append(total_loss)
-                msg = '(Iteration {}) TRAIN LOSS:{:.4f} CER:{:.2f}% LR:{:.7f} TOTAL TIME:{:.7f}'.format(
-                    (it + 1), total_loss / n_tasks, total_cer * 100 / max(total_char, 1), self.get_lr(opt), total_time)
+                if discriminator is None:
+                    msg = '(Iteration {}) TRAIN LOSS:{:.4f} CER:{:.2f}% LR:{:.7f} TOTAL TIME:{:.7f}'.format(
+                        (it + 1), total_loss / n_tasks, total_cer * 100 / max(total_char, 1), self.get_lr(opt), total_time)
+                elif adversarial:
+                    msg = ('(Iteration {}) TRAIN LOSS:{:.4f} DISC LOSS:{:.4f} ENC LOSS:{:.4f} CER:{:.2f}% LR:{:.7f} TOTAL TIME:{:.7f}'
+                           .format((it + 1), total_loss / n_tasks, total_disc_loss / n_tasks, total_enc_loss / n_tasks,
+                                   total_cer * 100 / max(total_char, 1), self.get_lr(opt), total_time))
+                else:
+                    msg = '(Iteration {}) TRAIN LOSS:{:.4f} DISC LOSS:{:.4f} CER:{:.2f}% LR:{:.7f} TOTAL TIME:{:.7f}'.format(
+                        (it + 1), total_loss / n_tasks, total_disc_loss / n_tasks, total_cer * 100 / max(total_char, 1),
+                        self.get_lr(opt), total_time)
                 if rank == 0:
                     print(msg)
                 logging.info(msg)
@@ -1168,8 +1271,10 @@ class JointTrainer():
                         print(msg, flush=True)
                     logging.info(msg)
                 if (it + 1) % evaluate_every == 0:                         # joint_trainer.py:306-380
-                    save_fn = lambda metrics, best_model: save_joint_model(model, vocab, (it + 1), opt, metrics, args,
-                                                                           best_model=best_model)
+                    def save_fn(metrics, best_model):
+                        save_joint_model(model, vocab, (it + 1), opt, metrics, args, best_model=best_model)
+                        if discriminator is not None and rank == 0:       # joint_trainer.py:358-359, 369-370
+                            save_discriminator(discriminator, (it + 1), opt_disc, args, best_model=best_model)
                     stop, best_valid_val, count_stop = run_validation(
                         fob, model, vocab, valid_loader_list, it, args, history, loss_type, save_fn, early_stop_criteria,
                         early_stop_val, best_valid_val, count_stop, rank)
