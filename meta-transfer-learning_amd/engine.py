@@ -182,17 +182,18 @@ class _DecodeSession:
         eng.gemm(0, 1, rows, width, hp.r, self.ta.data_ptr(), hp.r, o(name + '_linear_b.weight'), hp.r, dst, ldc or width,
                  bias=o(name + '_linear_b.bias'))
 
-    def _attend(self, q, kbuf, vbuf, kv_rows, kv_stride, out):
-        # one query row per (b, h): scores over kv_rows keys, softmax, weighted sum of the values
+    def _attend(self, q, kbuf, vbuf, kv_rows, k_stride, v_stride, out):
+        # one query row per (b, h): scores over kv_rows keys, softmax, weighted sum of the values; k_stride / v_stride: floats from one
+        # row's keys / values to the next row's (rows of h d_k and of h d_v floats: two numbers unless d_k = d_v), 0 for a shared memory
         eng, hp, B = self.eng, self.eng.hp, self.B
         h, dk, dv = hp.h, hp.dk, hp.dv
         hk, hv, ldS = h * dk, h * dv, self.ldS
-        eng.gemm(0, 1, 1, kv_rows, dk, q, hk, kbuf, hk, self.Sc.data_ptr(), ldS, batch=B * h, H=h, sA=(hk, dk), sB=(kv_stride, dk),
+        eng.gemm(0, 1, 1, kv_rows, dk, q, hk, kbuf, hk, self.Sc.data_ptr(), ldS, batch=B * h, H=h, sA=(hk, dk), sB=(k_stride, dk),
                  sC=(h * ldS, ldS))
         check(eng.lib.mtl_softmax_mask_fwd(eng.stream, self.Sc.data_ptr(), None, 0, 1.0 / float(hp.temperature), B, h, 1, kv_rows,
                                            ldS, None, 1.0, None), 'softmax')
         eng.gemm(0, 0, 1, dv, kv_rows, self.Sc.data_ptr(), ldS, vbuf, hv, out, hv, batch=B * h, H=h, sA=(h * ldS, ldS),
-                 sB=(kv_stride, dv), sC=(hv, dv))
+                 sB=(v_stride, dv), sC=(hv, dv))
 
     def _attend_groups(self, q, kbuf, vbuf, kv_rows, out):
         # cross-attention of `groups` utterances with W = B / groups query rows each: the same two strided-batch products and softmax
@@ -232,7 +233,7 @@ class _DecodeSession:
                 self._lowrank(sa, 'query', cur.data_ptr(), B, self.tq.data_ptr())
                 self._lowrank(sa, 'key', cur.data_ptr(), B, self.kc[i].data_ptr() + 4 * t * hk, ldc=S * hk)      # row t of the cache
                 self._lowrank(sa, 'value', cur.data_ptr(), B, self.vc[i].data_ptr() + 4 * t * hv, ldc=S * hv, width=hv)
-                self._attend(self.tq.data_ptr(), self.kc[i].data_ptr(), self.vc[i].data_ptr(), t + 1, S * hk, self.to.data_ptr())
+                self._attend(self.tq.data_ptr(), self.kc[i].data_ptr(), self.vc[i].data_ptr(), t + 1, S * hk, S * hv, self.to.data_ptr())
             if self.fast:
                 eng.gemm(0, 1, B, d, hv, self.to.data_ptr(), hv, self.Wso[i].data_ptr(), hv, self.tob.data_ptr(), d,
                          bias=o('self_attn.output_linear_b.bias'))
@@ -253,7 +254,8 @@ class _DecodeSession:
             elif self.groups > 1:
                 self._attend_groups(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.to.data_ptr())
             else:
-                self._attend(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.cross_stride * hk, self.to.data_ptr())
+                self._attend(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.cross_stride * hk,
+                             self.cross_stride * hv, self.to.data_ptr())
             if self.fast:
                 eng.gemm(0, 1, B, d, hv, self.to.data_ptr(), hv, self.Wco[i].data_ptr(), hv, self.tob.data_ptr(), d,
                          bias=o('encoder_attn.output_linear_b.bias'))
@@ -920,21 +922,22 @@ class PassEngine:
                                         delta.data_ptr(), dq.data_ptr(), dkk.data_ptr(), dvv.data_ptr(), hk, hk, hv), 'mtl_attn_bwd')
         else:
             Pm = A[tag + 'P']
-            dP = self.buf('_dP', (Bn, h, Tq, ldS))
-            sP = (h * Tq * ldS, Tq * ldS)
+            # (layer 0's decoder self-attention runs on the side stream under the encoder's backward: with Td = T4 the two would share one)
+            dP = self.buf('_dP.side' if self.on_side else '_dP', (Bn, h, Tq, ldS))
+            sS = (h * Tq * ldS, Tq * ldS)
             # dV = P^T dO ; dP = dO V^T ; dS = softmax'(P, dP)/temp ; dQ = dS K ; dK = dS^T Q
             Pv = A[tag + 'Pd'] if mP is not None else Pm                      # the probabilities that actually multiplied V
             self.gemm(1, 0, Tk, dv, Tq, Pv.data_ptr(), ldS, dO.data_ptr(), hv, dvv.data_ptr(), hv, batch=Bn * h, H=h,
-                      sA=sP, sB=(Tq * hv, dv), sC=(Tk * hv, dv))
+                      sA=sS, sB=(Tq * hv, dv), sC=(Tk * hv, dv))
             self.gemm(0, 1, Tq, Tk, dv, dO.data_ptr(), hv, v.data_ptr(), hv, dP.data_ptr(), ldS, batch=Bn * h, H=h,
-                      sA=(Tq * hv, dv), sB=(Tk * hv, dv), sC=sP)
+                      sA=(Tq * hv, dv), sB=(Tk * hv, dv), sC=sS)
             check(self.lib.mtl_softmax_bwd(self.stream, Pm.data_ptr(), dP.data_ptr(), 1.0 / float(hp.temperature),
                                            Bn * h * Tq, Tk, ldS, mP.data_ptr() if mP is not None else None, self.drop_scale),
                   'mtl_softmax_bwd')
             self.gemm(0, 0, Tq, dk, Tk, dP.data_ptr(), ldS, k.data_ptr(), hk, dq.data_ptr(), hk, batch=Bn * h, H=h,
-                      sA=sP, sB=(Tk * hk, dk), sC=(Tq * hk, dk))
+                      sA=sS, sB=(Tk * hk, dk), sC=(Tq * hk, dk))
             self.gemm(1, 0, Tk, dk, Tq, dP.data_ptr(), ldS, q.data_ptr(), hk, dkk.data_ptr(), hk, batch=Bn * h, H=h,
-                      sA=sP, sB=(Tq * hk, dk), sC=(Tk * hk, dk))
+                      sA=sS, sB=(Tq * hk, dk), sC=(Tk * hk, dk))
         kv_written = False
         for names, src, rows in groups:
             if dkv_hoisted is not None and names == 'kv':

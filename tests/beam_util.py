@@ -105,3 +105,29 @@ def oracle_beam_margin(model, padded_input, input_lengths, start_token, beam_wid
                     break
     model.train()
     return margin
+
+
+def oracle_greedy_margin(model, padded_input, input_lengths, start_token, steps):
+    """Smallest decision margin of oracle.refimpl.greedy_search on this batch: over all rows and steps, the gap between the best and the
+    second-best log-probability of the step.  Not oracle_beam_margin with W = 1: the greedy search does not stop at EOS and takes exactly
+    `steps` steps for every row (and the whole batch goes through the decoder at once, as greedy_search does).  CPU, oracle model."""
+    import torch.nn.functional as F
+    model.eval()
+    margin = float('inf')
+    with torch.no_grad():
+        f = model.conv(padded_input)
+        B, C, H, Wd = f.shape
+        mem = model.encoder(f.view(B, C * H, Wd).transpose(1, 2).contiguous(), input_lengths)
+        dec = model.decoder
+        ys = torch.full((B, 1), int(start_token), dtype=torch.int64)
+        for _ in range(steps):
+            Lq = ys.shape[1]
+            future = torch.triu(torch.ones(Lq, Lq, dtype=torch.bool), diagonal=1).unsqueeze(0).expand(B, Lq, Lq)
+            x = dec.trg_embedding(ys) + dec.positional_encoding.pe[:, :Lq]
+            for layer in dec.layers:
+                x = layer(x, mem, torch.ones(B, Lq, 1), future, torch.zeros(B, Lq, mem.shape[1], dtype=torch.bool))
+            best, ids = torch.topk(F.log_softmax(dec.output_linear(x)[:, -1], dim=1), 2, dim=1)
+            margin = min(margin, float((best[:, 0] - best[:, 1]).min()))
+            ys = torch.cat([ys, ids[:, :1]], dim=1)
+    model.train()
+    return margin

@@ -609,19 +609,20 @@ def test_sharded_bench_on_manifest_like_batches_equals_single_rank():
     assert abs(j1['theta_checksum'][0] - j2['theta_checksum'][0]) < 1e-5 * abs(j1['theta_checksum'][0])
 
 
-def test_dropout_pass_matches_oracle_with_the_same_masks():
-    """--dropout 0.1 (README config, SURVEY Q8): the keep-masks the HIP pass drew are replayed inside the oracle, so
-    forward and backward must agree exactly like the dropout-free pass (the masks themselves come from Philox, not from
-    torch's RNG stream, which is why parity with the reference is defined only given the masks)."""
+def _dropout_pass_parity(cfg, spec, batch, on_model=None):
+    """the body of test_dropout_pass_matches_oracle_with_the_same_masks for any model and batch (tests/test_unfused_attention_gpu.py
+    runs it on a model the fused attention kernel does not serve); on_model(model) is called before the first pass
+    -> (model, per-tensor gradient errors)"""
     from oracle import refimpl as R
-    z, cfg, spec = gu.load('F0')
     mtl_amd, args, vocab, model = make(cfg, spec)
     args.dropout = 0.1
     torch.manual_seed(123456)
     model = mtl_amd.init_transformer_model(args, vocab, r=cfg['r']).cuda()
     model.train()
+    if on_model is not None:
+        on_model(model)
     oracle = R.build_model(cfg)
-    (x, lens, y) = gu.batches_for(cfg, spec, 0, z['data_call_index'])[0][0]
+    (x, lens, y) = batch
     out = model.pass_forward(x.cuda(), lens, y)
     g = torch.zeros_like(model.flat_grad)
     model.pass_backward(g, 1.0)
@@ -656,6 +657,15 @@ def test_dropout_pass_matches_oracle_with_the_same_masks():
     assert 'dec_in.me' not in model.engine.arena
     pr0, _, _ = oracle(x, lens, y)
     assert float((out_e['pred'].cpu() - pr0).norm() / pr0.norm()) < 1e-5
+    return model, errs
+
+
+def test_dropout_pass_matches_oracle_with_the_same_masks():
+    """--dropout 0.1 (README config, SURVEY Q8): the keep-masks the HIP pass drew are replayed inside the oracle, so
+    forward and backward must agree exactly like the dropout-free pass (the masks themselves come from Philox, not from
+    torch's RNG stream, which is why parity with the reference is defined only given the masks)."""
+    z, cfg, spec = gu.load('F0')
+    _dropout_pass_parity(cfg, spec, gu.batches_for(cfg, spec, 0, z['data_call_index'])[0][0])
 
 
 @pytest.mark.parametrize('dropout', [0.0, 0.1])
