@@ -20,8 +20,9 @@ import torch
 
 import re
 
-from . import _lib, _trace
+from . import _lib, _trace, convstack
 from ._lib import check
+from .convstack import CENSUS_NAMES, CENSUS_SLOTS      # noqa: F401  (the bound slots of the h2 operands; the trainer's h2 guard names them)
 
 PAD_ID, SOS_ID, EOS_ID = 0, 1, 2
 RELU, ACCUM = 1, 2
@@ -343,8 +344,6 @@ def beam_unpack(state, U, W, S, start_token, eos_id):
     return out
 
 
-CENSUS_SLOTS = 9    # bound slots of the h2 operands: 0 y1, 1 p1, 2 y5, 3 dp2, 4 dy5, 5 dp1, 6 p2, (7: weights, not counted) 8 de0
-CENSUS_NAMES = {0: 'conv0 out', 1: 'pool1', 2: 'conv5 out', 3: 'd pool2', 4: 'd conv5 out', 5: 'd pool1', 6: 'pool2', 8: 'd input-linear out'}
 STAGE_RING = 6      # pinned staging buffers per slot (prepare_tasks): > pipeline depth (default 2) + 2
 
 _LAYER_BUF = re.compile(r'^([de])(\d+)\.(.+)$')
@@ -745,7 +744,7 @@ class PassEngine:
             return
         n = t.numel() // self.nt
         check(self.lib.mtl_h2_census(self.stream, t.data_ptr(), n, amax_ptr, self.census.data_ptr() + 32 * slot, self.nt, n,
-                                     12 * _lib.AMAX_SLOTS, 4 * CENSUS_SLOTS), 'mtl_h2_census')
+                                     convstack.AMAX_STRIDE, 4 * CENSUS_SLOTS), 'mtl_h2_census')
 
     def colsum(self, x, rows, cols, out, amax=None):
         ws = self.scratch(self.lib.mtl_colsum_workspace(rows, cols))
@@ -1249,9 +1248,9 @@ class PassEngine:
         meta-step are independent given theta0): x is (nt * B, 1, F, T) -- or (B, 1, F, T) when every task sees the SAME batch (the
         shared validation batch) -- and task t reads its parameters at theta + t * sP floats: sP = 0 for the training passes (all
         at theta0), sP = layout.total for the validation passes at the theta' stack.  Every transformer kernel runs ONCE over the
-        rows of all tasks (task = outermost batch index of the products, row group of LayerNorm / embedding / loss); the
-        convolutions and the two products around the encoder's input Linear are issued per task.  loss is (nt,), hyp
-        (nt * B, Td)."""
+        rows of all tasks (task = outermost batch index of the products, row group of LayerNorm / embedding / loss); so do the
+        convolutions and the products around the encoder's input Linear in the x3 and h2 modes: one launch over the samples of all
+        tasks (convstack.py; the fp32 convolutions are issued per task).  loss is (nt,), hyp (nt * B, Td)."""
         hp, L, lib, st = self.hp, self.L, self.lib, self.stream
         nt = int(meta.get('nt', 1))
         self.trim_pool()
@@ -1265,9 +1264,7 @@ class PassEngine:
         if Bx not in (B, nt * B) or T != meta['T']:
             raise ValueError('input batch does not match the prepared batch')
         sX = B * F * T if Bx == nt * B and nt > 1 else 0          # task stride of the input (0: one batch shared by all tasks)
-        T2, F2 = T // 2, F // 2
-        T4, F4 = T2 // 2, F2 // 2
-        if F4 * 128 != hp.d_in:
+        if F // 2 // 2 * 128 != hp.d_in:
             raise ValueError('dim_input %d does not match %d frequency bins' % (hp.d_in, F))
         self.nt, self.sP = nt, int(sP)
         try:
@@ -1279,11 +1276,9 @@ class PassEngine:
         hp, L, lib, st = self.hp, self.L, self.lib, self.stream
         sP = self.sP
         B = meta['B']
-        T2, F2 = T // 2, F // 2
-        T4, F4 = T2 // 2, F2 // 2
-        ntw = nt if sP else 1                                       # distinct parameter sets of this pass
+        T4 = (T // 2) // 2
         P = theta.data_ptr()
-        o = lambda n, t=0: P + 4 * (L.off(n) + t * self.sP)
+        o = lambda n: P + 4 * L.off(n)
         d, V = hp.d, hp.V
         Td, ids, n_nonpad = meta['Td'], meta['ids'], meta['n_nonpad']
         self._seed_ptr, self._site = meta['seed'], 0
@@ -1291,149 +1286,13 @@ class PassEngine:
         Me, Md = B * T4, B * Td                                     # encoder / decoder rows PER TASK
         Bt = nt * B
 
-        # ---- VGG front-end (per task: its own weights in the validation pass, its own tensor bounds) ----
-        y1 = self.buf('y1', (Bt, T, F, 64))
-        x3, h2 = self.conv_x3, self.conv_h2
-        # h2: device bounds max|tensor| (64 slots each) of y1, p1, y5 | dp2, dy5, dp1 -- raised by the producers' epilogues
-        # (forward) or written by the bias-gradient column sums (backward)
-        # (6, 7, 8: p2, the permuted input_linear weight, de0 -- operands of the two h2 GEMMs around the encoder's input Linear)
-        amax = self.buf('amax', (nt, 12, _lib.AMAX_SLOTS))
-        am_ = (lambda i, t=0: amax.data_ptr() + 4 * _lib.AMAX_SLOTS * (12 * t + i)) if h2 else (lambda i, t=0: None)
-        if h2:
-            check(lib.mtl_memset_zero(st, amax.data_ptr(), nt * 12 * 4 * _lib.AMAX_SLOTS), 'mtl_memset_zero')
-        xp = lambda t: x.data_ptr() + 4 * t * sX
-        if nt > 1:      # every task's samples in one launch (task = grid dimension; sX = 0: the shared validation batch)
-            check(lib.mtl_conv0_relu_fwd_tb(st, x.data_ptr(), o('conv.0.weight'), o('conv.0.bias'), y1.data_ptr(), B, T, F, am_(0), nt, sX,
-                                            sP, sP, 12 * _lib.AMAX_SLOTS), 'conv0')
-        else:
-            for t in range(nt):
-                check(lib.mtl_conv0_relu_fwd(st, xp(t), o('conv.0.weight', t), o('conv.0.bias', t), y1[t * B:].data_ptr(), B, T, F,
-                                             am_(0, t)), 'conv0')
-        # tasks of different frame counts stacked at the widest (prepare_tasks(frames=...)): every convolution output that another
-        # convolution reads is cleared beyond its task's own frames, which is the zero border the task's own pass has there; p2's tail
-        # rows are encoder padding (keep_enc = 0: nothing reads them, no gradient reaches them)
-        widths = meta.get('widths')
-        tails = (lambda buf_, T_, row_, shift_: check(lib.mtl_zero_tails(st, buf_.data_ptr(), Bt, T_, row_, widths, shift_, B), 'mtl_zero_tails')) \
-            if widths is not None else (lambda *a_: None)
-        tails(y1, T, F * 64, 0)
-        wf, wd = {}, {}
-        wprep = lib.mtl_conv3x3_wprep_h2 if h2 else (lib.mtl_conv3x3_wprep_x3 if x3 else lib.mtl_conv3x3_wprep)
-        if h2:
-            conv_fwd = lambda s_, x_, w_, b_, y_, ai, ao, *dims: lib.mtl_conv3x3_relu_fwd_h2(s_, x_, ai, w_, b_, y_, ao, *dims)
-            conv_fwd_pool = lambda s_, x_, w_, b_, y_, a_, ai, ao, *dims: lib.mtl_conv3x3_relu_pool_fwd_h2(
-                s_, x_, ai, w_, b_, y_, a_, ao, *dims)
-        else:
-            f1 = lib.mtl_conv3x3_relu_fwd_x3 if x3 else lib.mtl_conv3x3_relu_fwd
-            f2 = lib.mtl_conv3x3_relu_pool_fwd_x3 if x3 else lib.mtl_conv3x3_relu_pool_fwd
-            conv_fwd = lambda s_, x_, w_, b_, y_, ai, ao, *dims: f1(s_, x_, w_, b_, y_, *dims)
-            conv_fwd_pool = lambda s_, x_, w_, b_, y_, a_, ai, ao, *dims: f2(s_, x_, w_, b_, y_, a_, *dims)
-        for idx, cin, cout in ((2, 64, 64), (5, 64, 128), (7, 128, 128)):
-            if h2:      # two fp16 pieces of every (scaled) weight + the scale
-                nb = lib.mtl_conv3x3_wprep_h2_bytes(cout, cin)
-                nb = (nb + 255) // 256 * 256
-                wf[idx] = self.buf('wf%d' % idx, (ntw, nb), torch.uint8)
-                wd[idx] = self.buf('wd%d' % idx, (ntw, nb), torch.uint8)
-            elif x3:    # three exact bf16 pieces of every weight, [piece][tap][cin/32][cout][32]
-                wf[idx] = self.buf('wf%d' % idx, (ntw, 3, 9, cin, cout), torch.bfloat16)
-                wd[idx] = self.buf('wd%d' % idx, (ntw, 3, 9, cout, cin), torch.bfloat16)
-            else:
-                wf[idx] = self.buf('wf%d' % idx, (ntw, 9, cin, cout))
-                wd[idx] = self.buf('wd%d' % idx, (ntw, 9, cout, cin))
-            if not h2:
-                for t in range(ntw):
-                    check(wprep(st, o('conv.%d.weight' % idx, t), wf[idx][t].data_ptr(), wd[idx][t].data_ptr(), cout, cin), 'wprep')
-        if h2 and ntw > 1:      # all three layers of ALL parameter sets (the theta' stack): one call (two launches)
-            spec = []
-            for idx, cin, cout in ((2, 64, 64), (5, 64, 128), (7, 128, 128)):
-                spec += [o('conv.%d.weight' % idx), wf[idx].data_ptr(), wd[idx].data_ptr(), cout, cin]
-            check(lib.mtl_conv3x3_wprep_h2_batch_tb(st, 3, *spec, ntw, sP, wf[2].stride(0), wf[5].stride(0), wf[7].stride(0)), 'wprep')
-        elif h2:        # all three layers: one call (two launches) per parameter set
-            for t in range(ntw):
-                spec = []
-                for idx, cin, cout in ((2, 64, 64), (5, 64, 128), (7, 128, 128)):
-                    spec += [o('conv.%d.weight' % idx, t), wf[idx][t].data_ptr(), wd[idx][t].data_ptr(), cout, cin]
-                check(lib.mtl_conv3x3_wprep_h2_batch(st, 3, *spec), 'wprep')
-        p1 = self.buf('p1', (Bt, T2, F2, 64))
-        am1 = self.buf('am1', (Bt, T2, F2, 64), torch.uint8)
-        y5 = self.buf('y5', (Bt, T2, F2, 128))
-        p2 = self.buf('p2', (Bt, T4, F4, 128))
-        am2 = self.buf('am2', (Bt, T4, F4, 128), torch.uint8)
-        # (a single task with frames of its own -- a widened batch on a lane -- takes the several-task launches too: they skip its tail rows)
-        x3_only = x3 and not h2
-        if x3_only and (nt > 1 or widths is not None):
-            # the exact 3 x bf16 split, same structure as the h2 branch below: ONE launch per layer for the samples of all tasks
-            swb = lambda idx: wf[idx].stride(0) * wf[idx].element_size() if ntw > 1 else 0
-            skip = widths
-            check(lib.mtl_conv3x3_relu_pool_fwd_x3_tb(st, y1.data_ptr(), wf[2].data_ptr(), o('conv.2.bias'), p1.data_ptr(), am1.data_ptr(),
-                                                      B, T, F, 64, 64, nt, swb(2), sP, skip, 0), 'conv2')
-            tails(p1, T2, F2 * 64, 1)
-            check(lib.mtl_conv3x3_relu_fwd_x3_tb(st, p1.data_ptr(), wf[5].data_ptr(), o('conv.5.bias'), y5.data_ptr(), B, T2, F2, 64, 128,
-                                                 nt, swb(5), sP, skip, 1), 'conv5')
-            tails(y5, T2, F2 * 128, 1)
-            check(lib.mtl_conv3x3_relu_pool_fwd_x3_tb(st, y5.data_ptr(), wf[7].data_ptr(), o('conv.7.bias'), p2.data_ptr(), am2.data_ptr(),
-                                                      B, T2, F2, 128, 128, nt, swb(7), sP, skip, 1), 'conv7')
-            if skip is not None:
-                tails(p2, T4, F4 * 128, 2)
-                tails(am1, T2, F2 * 64 // 4, 1)
-                tails(am2, T4, F4 * 128 // 4, 2)
-        elif h2 and (nt > 1 or widths is not None):
-            # the samples of all tasks in ONE launch per layer (per-task bounds, weights and biases by stride): a persistent grid's
-            # prologue, tail and launch boundary are paid once instead of nt times (2-14 % of a layer: tools/probe/conv_batch_tasks.py);
-            # per task bitwise the per-task launches (tests/test_ops_gpu.py)
-            AS = 12 * _lib.AMAX_SLOTS
-            sw = lambda idx: wf[idx].stride(0) if ntw > 1 else 0
-            # (tasks with frame counts of their own: the launches leave out the pixel-tile rows beyond a task's frames -- `skip` -- and
-            # everything a later kernel reads there is cleared: activations, pooled maps and their arg-max bytes)
-            skip = widths
-            check(lib.mtl_conv3x3_relu_pool_fwd_h2_tb(st, y1.data_ptr(), am_(0), wf[2].data_ptr(), o('conv.2.bias'), p1.data_ptr(), am1.data_ptr(),
-                                                      am_(1), B, T, F, 64, 64, nt, sw(2), sP, AS, AS, skip, 0), 'conv2')
-            tails(p1, T2, F2 * 64, 1)
-            check(lib.mtl_conv3x3_relu_fwd_h2_tb(st, p1.data_ptr(), am_(1), wf[5].data_ptr(), o('conv.5.bias'), y5.data_ptr(), am_(2),
-                                                 B, T2, F2, 64, 128, nt, sw(5), sP, AS, AS, skip, 1), 'conv5')
-            tails(y5, T2, F2 * 128, 1)
-            check(lib.mtl_conv3x3_relu_pool_fwd_h2_tb(st, y5.data_ptr(), am_(2), wf[7].data_ptr(), o('conv.7.bias'), p2.data_ptr(), am2.data_ptr(),
-                                                      am_(6), B, T2, F2, 128, 128, nt, sw(7), sP, AS, AS, skip, 1), 'conv7')
-            if skip is not None:
-                tails(p2, T4, F4 * 128, 2)
-                tails(am1, T2, F2 * 64 // 4, 1)          # (bytes, four to a float)
-                tails(am2, T4, F4 * 128 // 4, 2)
-        else:
-            def c2(t, tw, sl):
-                check(conv_fwd_pool(st, y1[sl].data_ptr(), wf[2][tw].data_ptr(), o('conv.2.bias', t), p1[sl].data_ptr(), am1[sl].data_ptr(),
-                                    am_(0, t), am_(1, t), B, T, F, 64, 64), 'conv2')
-
-            def c5(t, tw, sl):
-                check(conv_fwd(st, p1[sl].data_ptr(), wf[5][tw].data_ptr(), o('conv.5.bias', t), y5[sl].data_ptr(), am_(1, t), am_(2, t),
-                               B, T2, F2, 64, 128), 'conv5')
-
-            def c7(t, tw, sl):
-                check(conv_fwd_pool(st, y5[sl].data_ptr(), wf[7][tw].data_ptr(), o('conv.7.bias', t), p2[sl].data_ptr(), am2[sl].data_ptr(),
-                                    am_(2, t), am_(6, t), B, T2, F2, 128, 128), 'conv7')
-            per_task = [(t, (t if sP else 0), slice(t * B, (t + 1) * B)) for t in range(nt)]
-            if widths is None:
-                for a_ in per_task:          # task by task
-                    c2(*a_)
-                    c5(*a_)
-                    c7(*a_)
-            else:                            # layer by layer: a layer's tails are cleared (all tasks at once) before the next layer reads them
-                for a_ in per_task:
-                    c2(*a_)
-                tails(p1, T2, F2 * 64, 1)
-                for a_ in per_task:
-                    c5(*a_)
-                tails(y5, T2, F2 * 128, 1)
-                for a_ in per_task:
-                    c7(*a_)
-
-        if h2 and self.census is not None:          # (stream order: every producer epilogue has raised its bound by now)
-            for slot, t_ in ((0, y1), (1, p1), (2, y5), (6, p2)):
-                self._census(slot, t_, am_(slot))
+        # ---- VGG front-end (convstack.py) ----
+        # what this pass runs on is decided here, once: the backward goes by this record, not by the engine's attributes of its time
+        S = dict(theta=theta, x=x, B=B, T=T, F=F, meta=meta, nt=nt, sP=sP, sX=sX, **convstack.decide(self, nt, meta.get('widths')))
+        front = convstack.Front(self, S)
+        front.convs_fwd()
 
         # ---- encoder ----
-        wp = self.buf('wp_in', (ntw, d, hp.d_in))
-        # am_(7): max|w| rides along; the theta' stack in one launch
-        check(lib.mtl_permute_hc_tb(st, o('encoder.input_linear.weight'), wp.data_ptr(), d, 128, F4, 0, am_(7), ntw, self.sP, d * hp.d_in,
-                                    12 * _lib.AMAX_SLOTS), 'permute')
         # decoder prologue: embedding (+ PE, dropout) and layer 0's self-attention block read the labels and theta only
         def dec_prologue():
             d0_ = self.buf('dec_in.y', (nt * Md, d))
@@ -1446,24 +1305,10 @@ class PassEngine:
             return d0_, self.mha_fwd('d0.sa.', P, 'decoder.layers.0.self_attn.', d0_.data_ptr(), B, Td, d0_.data_ptr(), Td, klen_dec, 1,
                                      keep_dec)
         pro_done = None
-        self.dec0_on_side = bool(self.use_side_stream and hp.n_dec > 0)
-        if self.dec0_on_side:
+        S['dec0_on_side'] = bool(self.use_side_stream and hp.n_dec > 0)
+        if S['dec0_on_side']:
             (d0, a0), pro_done = self.run_on_side(dec_prologue)      # under the input Linear and the encoder
-        e0 = self.buf('e0', (nt * Me, d))
-        # the encoder's input Linear (5120 -> 512) and its data gradient: 'x3' = one task-batched launch each on the bf16-split engine
-        # (exact 3-piece operands, no bounds needed; MTL_IN_LINEAR=x3), 'h2' (default) = one task-batched launch each on two fp16 pieces
-        # (mtl_gemm_h2_tb: the same tile engine with three MFMAs per step)
-        self.in_h2 = h2 and self.in_linear == 'h2'
-        if self.in_h2:      # the two compute-bound products of the pass on fp16 pairs: e0 = p2 . wp^T here, dp2 = de0 . wp in the backward
-            am_st = 12 * _lib.AMAX_SLOTS                          # floats between two tasks' bounds
-            # ONE task-batched launch on the tile engine of mtl_gemm_x3.hip (per-task bounds by stride)
-            check(lib.mtl_gemm_h2_tb(st, 1, Me, d, hp.d_in, p2.data_ptr(), hp.d_in, am_(6), am_st, wp.data_ptr(), hp.d_in, am_(7),
-                                     am_st if sP else 0, e0.data_ptr(), d, o('encoder.input_linear.bias'), None, 0, nt,
-                                     Me * hp.d_in, d * hp.d_in if sP else 0, Me * d, self.sP, self.gemm_ws.data_ptr(), self.gemm_ws.numel() * 4),
-                  'mtl_gemm_h2_tb')
-        else:
-            self.gemm(0, 1, Me, d, hp.d_in, p2.data_ptr(), hp.d_in, wp.data_ptr(), hp.d_in, e0.data_ptr(), d,
-                      bias=o('encoder.input_linear.bias'), task=(Me * hp.d_in, d * hp.d_in if sP else 0, Me * d, self.sP, 0))
+        e0 = front.linear_fwd()
         ex = self.buf('enc_in.y', (nt * Me, d))
         self.ln_fwd(e0.data_ptr(), None, o('encoder.layer_norm_input.weight'), o('encoder.layer_norm_input.bias'),
                     self.pe_enc.data_ptr(), None, ex.data_ptr(), self.buf('enc_in.xhat', (nt * Me, d)).data_ptr(),
@@ -1508,9 +1353,8 @@ class PassEngine:
         else:
             check(lib.mtl_ce_argmax_fwd_g(st, pred.data_ptr(), gold_ptr, nt * Md, V, V, PAD_ID, float(smoothing), meta['inv_count'],
                                           lse.data_ptr(), hyp.data_ptr(), rowloss.data_ptr(), loss.data_ptr(), Md), 'ce_fwd')
-        self.saved = dict(theta=theta, x=x, B=B, T=T, F=F, Td=Td, n_nonpad=n_nonpad, smoothing=float(smoothing), meta=meta,
-                          klen_enc=klen_enc, klen_dec=klen_dec, keep_enc=keep_enc, keep_dec=keep_dec, dec_last=cur,
-                          enc_inputs=enc_inputs, nt=nt, sP=self.sP, sX=sX)
+        self.saved = dict(S, Td=Td, n_nonpad=n_nonpad, smoothing=float(smoothing), klen_enc=klen_enc, klen_dec=klen_dec, keep_enc=keep_enc,
+                          keep_dec=keep_dec, dec_last=cur, enc_inputs=enc_inputs)
         if self.forward_hook is not None:
             self.forward_hook(self)
         # T4 / frames: the extent of the arena's encoder-side activations (a widened stand-alone pass, PassEngine.forward, carries
@@ -1792,14 +1636,13 @@ class PassEngine:
         if nt > 1 and (sG != L.total or grad.numel() != nt * L.total or dpred is not None):
             raise ValueError('a task-batched backward accumulates into a (tasks, layout.total) gradient stack')
         assert grad.numel() == L.total * nt and grad.is_contiguous()
-        sP, sG, sX = self.sP, self.sG, S['sX']
+        sP, sG = self.sP, self.sG
         theta = S['theta']
         P, G = theta.data_ptr(), grad.data_ptr()
-        o = lambda n, t=0: P + 4 * (L.off(n) + t * sP)
-        g = lambda n, t=0: G + 4 * (L.off(n) + t * sG)
-        B, T, F, Td = S['B'], S['T'], S['F'], S['Td']
-        T2, F2 = T // 2, F // 2
-        T4, F4 = T2 // 2, F2 // 2
+        o = lambda n: P + 4 * L.off(n)
+        g = lambda n: G + 4 * L.off(n)
+        B, T, Td = S['B'], S['T'], S['Td']
+        T4 = (T // 2) // 2
         Me, Md, d, V = B * T4, B * Td, hp.d, hp.V                   # rows PER TASK
         keep_enc, keep_dec = S['keep_enc'], S['keep_dec']
 
@@ -1845,7 +1688,7 @@ class PassEngine:
             self.mha_bwd('d%d.ca.' % i, P, G, pre + 'encoder_attn.', dcur.data_ptr(), sa_y.data_ptr(), B, Td, mem_ptr, T4, keep_dec,
                          dnext.data_ptr(), dmem.data_ptr(), i != hp.n_dec - 1, dkv_hoisted=dkv_all[i] if hoisted else None)
             dcur, dnext = dnext, dcur
-            if i == 0 and getattr(self, 'dec0_on_side', False):
+            if i == 0 and S['dec0_on_side']:
                 # layer 0's self-attention block and the embedding feed parameter gradients only (the encoder's backward needs dmem,
                 # which is complete): side stream, under the encoder's backward.  dcur / dnext are not touched by the main stream
                 # again; the block's weight-gradient products are logged like every layer's and issued behind it on the same stream.
@@ -1893,169 +1736,15 @@ class PassEngine:
                     None, de0.data_ptr(), g('encoder.layer_norm_input.weight'), g('encoder.layer_norm_input.bias'), Me,
                     dsum=g('encoder.input_linear.bias'))
         self.flush_layer_wgrads()       # the encoder stack's weight gradients
-        p2, y5, p1, y1 = A['p2'], A['y5'], A['p1'], A['y1']
-        dwp = self.buf('_dwp', (nt, d, hp.d_in))
-        dp2 = self.buf('_dp2', (nt * B, T4, F4, 128))
-        h2 = self.conv_h2
-        amax = A['amax']
-        am_ = (lambda i, t=0: amax.data_ptr() + 4 * _lib.AMAX_SLOTS * (12 * t + i)) if h2 else (lambda i, t=0: None)   # y1, p1, y5 | dp2, dy5, dp1
-        am_st = 12 * _lib.AMAX_SLOTS
-        if self.in_h2 and nt > 1:
-            check(lib.mtl_absmax_f32_tb(st, de0.data_ptr(), Me * d, am_(8), nt, Me * d, am_st), 'mtl_absmax_f32')
-        elif self.in_h2:
-            for t in range(nt):
-                check(lib.mtl_absmax_f32(st, de0[t * Me:].data_ptr(), Me * d, am_(8, t)), 'mtl_absmax_f32')
-        if self.in_h2:
-            self._census(8, de0, am_(8))
-        if self.in_h2:      # dW = de0^T . p2 on fp16 pairs too: both bounds (slots 8, 6) exist for the data gradient below
-            check(lib.mtl_gemm_h2_tn_tb(st, d, hp.d_in, Me, de0.data_ptr(), d, am_(8), am_st, p2.data_ptr(), hp.d_in, am_(6), am_st,
-                                        dwp.data_ptr(), hp.d_in, nt, Me * d, Me * hp.d_in, d * hp.d_in), 'mtl_gemm_h2_tn_tb')
-        else:
-            self.gemm(1, 0, d, hp.d_in, Me, de0.data_ptr(), d, p2.data_ptr(), hp.d_in, dwp.data_ptr(), hp.d_in,
-                      task=(Me * d, Me * hp.d_in, d * hp.d_in, 0, 0))
-        check(lib.mtl_permute_hc_tb(st, dwp.data_ptr(), g('encoder.input_linear.weight'), d, 128, F4, 1, None, nt, d * hp.d_in, sG, 0), 'permute_inv')
+        # input Linear and VGG front-end (convstack.py), in the mode the forward recorded
+        front = convstack.Front(self, S, G, sG)
+        front.linear_bwd(de0)
         if self.slice_hook is not None:
             self.flush_ln_reduce()         # the encoder's LayerNorms (+ the input LayerNorm): their partials were all produced on this stream
             self._slice_done('encoder')
-        if self.in_h2:
-            # dp2 = (de0 . wp) gated by p2 > 0, straight from the un-transposed weight, all tasks in one launch
-            check(lib.mtl_gemm_h2_tb(st, 0, Me, hp.d_in, d, de0.data_ptr(), d, am_(8), am_st, A['wp_in'].data_ptr(), hp.d_in, am_(7),
-                                     am_st if sP else 0, dp2.data_ptr(), hp.d_in, None, p2.data_ptr(), hp.d_in, nt, Me * d,
-                                     d * hp.d_in if sP else 0, Me * hp.d_in, 0, None, 0), 'mtl_gemm_h2_tb')
-        else:
-            self.gemm(0, 0, Me, hp.d_in, d, de0.data_ptr(), d, A['wp_in'].data_ptr(), hp.d_in, dp2.data_ptr(), hp.d_in,
-                      gate=p2.data_ptr(), ldg=hp.d_in, task=(Me * d, d * hp.d_in if sP else 0, Me * hp.d_in, 0, 0))
-
+        front.linear_dgrad(de0)
         self.flush_side()
-        # ---- VGG front-end (per task) ----
-        dgrad_fn = lib.mtl_conv3x3_dgrad_x3 if self.conv_x3 else lib.mtl_conv3x3_dgrad
-
-        def conv_dgrad(t, dy, ai, am, w, act, dx, *dims, ao=None):
-            if h2:      # ao: slot that receives the bound of dx (the next layer's amax_dy)
-                return lib.mtl_conv3x3_dgrad_h2(st, dy, am_(ai, t), am, w, act, dx, am_(ao, t) if ao is not None else None, *dims)
-            return dgrad_fn(st, dy, am, w, act, dx, *dims)
-
-        # h2: the weight-gradient kernel's dy loaders also sum dy (bias gradient) and the data-gradient epilogue delivers the bound of
-        # its output, so the column-sum passes over dy5 (164 MB) and dp1 (82 MB) are not needed; dp2 keeps its pass (its bound has no
-        # other producer)
-
-        def wgrad(t, xa, axi, dy, adi, am, idx, Bq, Tq, Fq, cin, cout, db=None):
-            x3 = self.conv_x3
-            wsfn = lib.mtl_conv3x3_wgrad_x3_workspace if x3 else lib.mtl_conv3x3_wgrad_workspace
-            need = wsfn(Bq, Tq, Fq, cin, cout, 1 if am else 0)
-            ws = self.scratch(need)
-            if x3 and h2:
-                rc = lib.mtl_conv3x3_wgrad_h2(st, xa, am_(axi, t), dy, am_(adi, t), am, g('conv.%d.weight' % idx, t), db, ws, need, Bq, Tq,
-                                              Fq, cin, cout)
-            else:
-                fn = lib.mtl_conv3x3_wgrad_x3 if x3 else lib.mtl_conv3x3_wgrad
-                rc = fn(st, xa, dy, am, g('conv.%d.weight' % idx, t), ws, need, Bq, Tq, Fq, cin, cout)
-            check(rc, 'wgrad')
-
-        dy5 = self.buf('_dy5', (nt * B, T2, F2, 128))
-        dp1 = self.buf('_dp1', (nt * B, T2, F2, 64))
-        dy1 = self.buf('_dy1', (nt * B, T, F, 64))
-        x3_only = self.conv_x3 and not h2
-        merged = (h2 or x3_only) and (nt > 1 or S['meta'].get('widths') is not None)     # data gradients of conv7 / conv5: ONE launch over the samples of all tasks (see forward)
-        # the bias gradients of conv5 / conv2 ride on their weight-gradient launches (sums of dy in the loaders): always with h2 (the
-        # data-gradient epilogues also deliver the next bound), with the exact split in the several-task launches
-        f5 = f2 = h2 or (x3_only and merged)
-        xin = S['x']
-        # tasks with frame counts of their own (forward): the data gradients leave out the tile rows beyond a task's frames and those
-        # rows of their outputs are cleared right behind them -- bias sums, bounds and weight gradients read whole tensors
-        widths_b = S['meta'].get('widths')
-        skip = widths_b if merged else None
-        tails_b = (lambda buf_, T_, row_, shift_: check(lib.mtl_zero_tails(st, buf_.data_ptr(), nt * B, T_, row_, skip, shift_, B), 'mtl_zero_tails')) \
-            if skip is not None else (lambda *a_: None)
-        AS = 12 * _lib.AMAX_SLOTS
-        swd = lambda name: A[name].stride(0) * A[name].element_size() if (sP and nt > 1) else 0      # (bytes)
-
-        def layer7(t, dgrad):
-            tw, sl = (t if sP else 0), slice(t * B, (t + 1) * B)
-            am2_t = A['am2'][sl].data_ptr()
-            self.colsum(dp2[sl].data_ptr(), B * T4 * F4, 128, g('conv.7.bias', t), am_(3, t))
-            wgrad(t, y5[sl].data_ptr(), 2, dp2[sl].data_ptr(), 3, am2_t, 7, B, T2, F2, 128, 128)
-            if dgrad:
-                check(conv_dgrad(t, dp2[sl].data_ptr(), 3, am2_t, A['wd7'][tw].data_ptr(), y5[sl].data_ptr(), dy5[sl].data_ptr(),
-                                 B, T2, F2, 128, 128, ao=4 if f5 else None), 'dgrad7')
-
-        def layer5(t, dgrad):
-            tw, sl = (t if sP else 0), slice(t * B, (t + 1) * B)
-            if not f5:
-                self.colsum(dy5[sl].data_ptr(), B * T2 * F2, 128, g('conv.5.bias', t), am_(4, t))
-            wgrad(t, p1[sl].data_ptr(), 1, dy5[sl].data_ptr(), 4, None, 5, B, T2, F2, 64, 128, db=g('conv.5.bias', t) if f5 else None)
-            if dgrad:
-                check(conv_dgrad(t, dy5[sl].data_ptr(), 4, None, A['wd5'][tw].data_ptr(), p1[sl].data_ptr(), dp1[sl].data_ptr(),
-                                 B, T2, F2, 64, 128, ao=5 if f2 else None), 'dgrad5')
-
-        def layer2(t, wg=True, w0=True):
-            tw, sl = (t if sP else 0), slice(t * B, (t + 1) * B)
-            am1_t = A['am1'][sl].data_ptr()
-            if not f2:
-                self.colsum(dp1[sl].data_ptr(), B * T2 * F2, 64, g('conv.2.bias', t), am_(5, t))
-            if wg:
-                wgrad(t, y1[sl].data_ptr(), 0, dp1[sl].data_ptr(), 5, am1_t, 2, B, T, F, 64, 64, db=g('conv.2.bias', t) if f2 else None)
-            check(conv_dgrad(t, dp1[sl].data_ptr(), 5, am1_t, A['wd2'][tw].data_ptr(), y1[sl].data_ptr(), dy1[sl].data_ptr(),
-                             B, T, F, 64, 64), 'dgrad2')
-            if w0:
-                ws = self.scratch(lib.mtl_conv0_wgrad_workspace())
-                check(lib.mtl_conv0_wgrad(st, xin.data_ptr() + 4 * t * sX, dy1[sl].data_ptr(), g('conv.0.weight', t), g('conv.0.bias', t),
-                                          ws, B, T, F), 'wgrad0')
-
-        def wgrad_tb(xa, axi, dy, adi, am, idx, Tq, Fq, cin, cout, db):
-            """the weight (+ bias) gradients of all tasks of one layer in ONE launch (its partial slabs are dealt to the tasks: as many
-            slabs written and reduced as by one single-task launch)"""
-            need = lib.mtl_conv3x3_wgrad_x3_workspace(B, Tq, Fq, cin, cout, 1 if am else 0)
-            ws = self.scratch(need)
-            if x3_only:
-                check(lib.mtl_conv3x3_wgrad_x3_tb(st, xa, dy, am, g('conv.%d.weight' % idx), db, ws, need, B, Tq, Fq, cin, cout, nt, sG, sG),
-                      'wgrad_tb')
-                return
-            check(lib.mtl_conv3x3_wgrad_h2_tb(st, xa, am_(axi), dy, am_(adi), am, g('conv.%d.weight' % idx), db, ws, need, B, Tq, Fq, cin, cout,
-                                              nt, AS, AS, sG, sG), 'wgrad_tb')
-
-        if merged:
-            per = ((lib.mtl_colsum_workspace(B * T4 * F4, 128) // 4 + 3) // 4 * 4) * 4
-            check(lib.mtl_colsum_accum_tb(st, dp2.data_ptr(), B * T4 * F4, 128, g('conv.7.bias'), self.scratch(nt * per + 64), am_(3), nt, sG, AS),
-                  'colsum_tb')
-            wgrad_tb(y5.data_ptr(), 2, dp2.data_ptr(), 3, A['am2'].data_ptr(), 7, T2, F2, 128, 128, None)
-            if x3_only:
-                check(lib.mtl_conv3x3_dgrad_x3_tb(st, dp2.data_ptr(), A['am2'].data_ptr(), A['wd7'].data_ptr(), y5.data_ptr(), dy5.data_ptr(),
-                                                  B, T2, F2, 128, 128, nt, swd('wd7'), skip, 1), 'dgrad7')
-            else:
-                check(lib.mtl_conv3x3_dgrad_h2_tb(st, dp2.data_ptr(), am_(3), A['am2'].data_ptr(), A['wd7'].data_ptr(), y5.data_ptr(),
-                                                  dy5.data_ptr(), am_(4) if f5 else None, B, T2, F2, 128, 128, nt, swd('wd7'), AS, AS, skip, 1),
-                      'dgrad7')
-            tails_b(dy5, T2, F2 * 128, 1)
-            wgrad_tb(p1.data_ptr(), 1, dy5.data_ptr(), 4, None, 5, T2, F2, 64, 128, g('conv.5.bias'))
-            if x3_only:
-                check(lib.mtl_conv3x3_dgrad_x3_tb(st, dy5.data_ptr(), None, A['wd5'].data_ptr(), p1.data_ptr(), dp1.data_ptr(),
-                                                  B, T2, F2, 64, 128, nt, swd('wd5'), skip, 1), 'dgrad5')
-            else:
-                check(lib.mtl_conv3x3_dgrad_h2_tb(st, dy5.data_ptr(), am_(4), None, A['wd5'].data_ptr(), p1.data_ptr(), dp1.data_ptr(),
-                                                  am_(5) if f2 else None, B, T2, F2, 64, 128, nt, swd('wd5'), AS, AS, skip, 1), 'dgrad5')
-            tails_b(dp1, T2, F2 * 64, 1)
-            wgrad_tb(y1.data_ptr(), 0, dp1.data_ptr(), 5, A['am1'].data_ptr(), 2, T, F, 64, 64, g('conv.2.bias'))
-            # conv2's data gradient: one launch for all tasks too (its matrix kernel covers the even part of the 161-bin axis, the last
-            # column goes to the edge kernel: csrc/mtl_mfma.hip conv_dgrad_edge_kernel)
-            if x3_only:
-                check(lib.mtl_conv3x3_dgrad_x3_tb(st, dp1.data_ptr(), A['am1'].data_ptr(), A['wd2'].data_ptr(), y1.data_ptr(), dy1.data_ptr(),
-                                                  B, T, F, 64, 64, nt, swd('wd2'), skip, 0), 'dgrad2')
-            else:
-                check(lib.mtl_conv3x3_dgrad_h2_tb(st, dp1.data_ptr(), am_(5), A['am1'].data_ptr(), A['wd2'].data_ptr(), y1.data_ptr(),
-                                                  dy1.data_ptr(), None, B, T, F, 64, 64, nt, swd('wd2'), AS, 0, skip, 0), 'dgrad2')
-            tails_b(dy1, T, F * 64, 0)
-            ws = self.scratch(lib.mtl_conv0_wgrad_workspace())
-            check(lib.mtl_conv0_wgrad_tb(st, xin.data_ptr(), dy1.data_ptr(), g('conv.0.weight'), g('conv.0.bias'), ws, B, T, F, nt, sX, sG, sG),
-                  'wgrad0_tb')
-        else:
-            for t in range(nt):
-                layer7(t, True)
-                layer5(t, True)
-                layer2(t)
-        if h2 and self.census is not None:
-            for slot, t_ in ((3, dp2), (4, dy5), (5, dp1)):
-                self._census(slot, t_, am_(slot))
+        front.convs_bwd()
         self.join_side()
         self.flush_ln_reduce()     # the parameter / bias gradients of all 17 LayerNorms of the pass: one launch (after the join: one of
                                    # the 17 backward kernels ran on the side stream)
