@@ -775,6 +775,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef X3H_M16
 #define X3H_M16 1          // consumers of conv3x3_x3h_kernel on 16 x 16 x 32 matrix instructions (0: 32 x 32 x 16, A/B builds)
 #endif
+// routes of the two-piece fp16 data gradients with 64 output channels (A/B builds; 0 = the 32-channel consumer waves, WN = 2, of before)
+#ifndef X3H_DG2
+#define X3H_DG2 1          // un-pooling source, 64 reduction channels (conv2): 1 = 16 x 16 tiles, four consumer waves of 64 px x 64 ch
+#endif
+#ifndef X3H_DG5
+#define X3H_DG5 1          // dense source, 128 reduction channels (conv5): 64 px x 64 ch waves on 1 = 32 x 32 x 16, 2 = 16 x 16 x 32 instructions
+#endif                     // (2 is 6 % faster than 1, but sums in another order than the 32 x 32 x 16 kernel it replaces: last-bit differences)
 template <int NP>
 struct Split;
 template <>
@@ -1003,12 +1010,40 @@ __device__ inline X3Tile x3_tile(const ConvX3P& p, int id, X3Cur& c) {
     return t;
 }
 
+// The wave maximum of mtl_common.h goes through ds_bpermute with six lane-index registers, which the compiler computes once per kernel and
+// keeps (or spills) across the matrix loop.  SWZ: the same maximum from ds_swizzle (constant patterns) and two v_readlane, no index register
+// -- for the instantiations that have none to spare.  (A maximum does not depend on the order it is taken in: the same bits.)
+template <bool SWZ>
+__device__ __forceinline__ float x3_wave_max(float v) {
+    if constexpr (!SWZ) {
+        return wave_max(v);
+    } else {
+        v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (1 << 10) | 0x1f)));
+        v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (2 << 10) | 0x1f)));
+        v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (4 << 10) | 0x1f)));
+        v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (8 << 10) | 0x1f)));
+        v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (16 << 10) | 0x1f)));
+        return fmaxf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)));
+    }
+}
+template <bool SWZ>
+__device__ __forceinline__ float x3_amax_read(const float* a) {      // amax_read / amax_raise of mtl_common.h on x3_wave_max
+    return x3_wave_max<SWZ>(a[(threadIdx.x & (MTL_AMAX_SLOTS - 1)) * MTL_AMAX_STRIDE]);
+}
+template <bool SWZ>
+__device__ __forceinline__ void x3_amax_raise(float* a, float mx) {
+    mx = x3_wave_max<SWZ>(mx);
+    float* slot = a + (blockIdx.x & (MTL_AMAX_SLOTS - 1)) * MTL_AMAX_STRIDE;
+    if ((threadIdx.x & 63) == 0 && mx > *slot) atomicMax(reinterpret_cast<unsigned*>(slot), __float_as_uint(mx));
+}
+
 // WN = consumer waves along the output channels of a 128-pixel sub-tile (2 pixel halves x WN): 2 -> each wave owns 64 px x BN/2 ch,
 // 1 -> 64 px x BN ch.  The fragment reads of a wave feed TM x TN MFMA groups, (TM + TN) NP ds_read_b128 per TM TN groups: with
 // 64 output channels WN = 2 means 3 reads per group (two-piece fp16: LDS 100 % busy at 50 % matrix-pipe load), WN = 1 means 2.
 template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN>
 __global__ __launch_bounds__((2 * WN * G + 4) * 64) __attribute__((amdgpu_waves_per_eu(WN == 1 ? 4 : 1)))   // WN = 1: two workgroups per CU
 void conv3x3_x3h_kernel(ConvX3P p) {
+    constexpr bool SLIM = WN == 1 && EPI == EPI_DGRAD;             // 64 x 64 wave tiles + gated epilogue: every register counts (x3_wave_max, the epilogue)
     constexpr int CW = 2 * WN;                                      // consumer waves per 8 x 16 sub-tile
     constexpr int WTM = 64, WTN = BN / WN, TM = WTM / 32, TN = WTN / 32;
     constexpr int XH_HT = 8 * G + 2, XH_NPIX = XH_HT * XH_HF;      // halo of an (8 G) x 16 tile
@@ -1032,7 +1067,7 @@ void conv3x3_x3h_kernel(ConvX3P p) {
     if (tid >= NCONS + 64) {
         // ------------------------------------------------------------------ halo waves (3): gather, 3-way split, LDS image
         const int ptid = tid - NCONS - 64;
-        float sx = NP == 2 ? pow2_scale(amax_read(p.amax_in)) : 1.f;
+        float sx = NP == 2 ? pow2_scale(x3_amax_read<SLIM>(p.amax_in)) : 1.f;
         int sx_task = 0;
         X3Cur cur_scale, cur_halo;
         auto set_scale = [&](int qc) {          // the operand scale of the task that stage qc's tile belongs to
@@ -1040,18 +1075,20 @@ void conv3x3_x3h_kernel(ConvX3P p) {
             const int tk = x3_tile<G>(p, blockIdx.x + (qc / cch) * gridDim.x, cur_scale).b / p.Bt;
             if (tk != sx_task) {
                 sx_task = tk;
-                sx = pow2_scale(amax_read(p.amax_in + tk * p.sAmaxIn));
+                sx = pow2_scale(x3_amax_read<SLIM>(p.amax_in + tk * p.sAmaxIn));
             }
         };
         float4 hv[XH_NVA];
         uchar4 ha[XH_NVA];
-        unsigned hm[XH_NVA];
+        unsigned hm[SLIM ? 1 : XH_NVA];        // SLIM: the validity bits of all elements in hm[0] (the window position is re-derived at the commit)
         auto fetch_halo = [&](int q) {          // stage q: channels c*32 .. +31 of the halo pixels of its tile
             const int j = q / cch, c = q - j * cch;
             const X3Tile tl = x3_tile<G>(p, blockIdx.x + j * gridDim.x, cur_halo);
+            int pt = ptid;                      // (SLIM: the elements' lane terms are derived here, not kept -- spilled -- from the prologue)
+            if constexpr (SLIM) asm volatile("" : "+v"(pt));
 #pragma unroll
             for (int i = 0; i < XH_NVA; ++i) {
-                const int e = ptid + i * NHALO;
+                const int e = pt + i * NHALO;
                 const int hp = min(e >> 3, XH_NPIX - 1), c4 = (e & 7) * 4;
                 const int ht = hp / XH_HF, hf = hp - ht * XH_HF;
                 const int ts = tl.t0 + ht - 1, fs = tl.f0 + hf - 1;
@@ -1059,30 +1096,43 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                 const int tc = min(max(ts, 0), T - 1), fc = min(max(fs, 0), F - 1);
                 if (!UNPOOL) {
                     hv[i] = *reinterpret_cast<const float4*>(p.x + (((long)tl.b * T + tc) * F + fc) * Cin + c * BK + c4);
-                    hm[i] = ok ? 1u : 0u;
+                    if constexpr (SLIM) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
+                    else hm[i] = ok ? 1u : 0u;
                 } else {
                     const int tp = tc >> 1, fp = fc >> 1;
                     ok = ok && tp < Tp && fp < Fp;
+                    if constexpr (SLIM) {       // scalar base of the (sample, chunk) + one 32-bit offset for both loads: no 64-bit address pair per element
+                        const long sbase = (long)__builtin_amdgcn_readfirstlane(tl.b) * Tp * Fp * Cin + c * BK;
+                        const unsigned o = (unsigned)((min(tp, Tp - 1) * Fp + min(fp, Fp - 1)) * Cin + c4);
+                        ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + sbase + o);
+                        hv[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.x + sbase) + o * 4u);
+                    } else {
                     const long o = (((long)tl.b * Tp + min(tp, Tp - 1)) * Fp + min(fp, Fp - 1)) * Cin + c * BK + c4;
                     ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + o);
                     hv[i] = *reinterpret_cast<const float4*>(p.x + o);
-                    hm[i] = (ok ? 1u : 0u) | ((unsigned)(((fs & 1) << 1) | (ts & 1)) << 1);
+                    }
+                    if constexpr (SLIM) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
+                    else hm[i] = (ok ? 1u : 0u) | ((unsigned)(((fs & 1) << 1) | (ts & 1)) << 1);
                 }
             }
         };
         // (Splitting ahead of the swap barrier so that only the ds_writes sit between the two barriers was tried: the 84
         // extra live registers spill under the 168-VGPR cap of a 12-wave workgroup and every launch gets 15-40 % slower.)
         auto commit_halo = [&]() {
+            int pt = ptid;
+            if constexpr (SLIM) asm volatile("" : "+v"(pt));
 #pragma unroll
             for (int i = 0; i < XH_NVA; ++i) {
-                const int e = ptid + i * NHALO;
+                const int e = pt + i * NHALO;
                 if ((e >> 3) >= XH_NPIX) continue;
                 float4 v = hv[i];
-                const bool ok = hm[i] & 1u;
+                const bool ok = SLIM ? (hm[0] >> i) & 1u : hm[i] & 1u;
                 if (!UNPOOL) {
                     v = mask4(v, ok ? 15u : 0u);
                 } else {
-                    const unsigned sub = hm[i] >> 1;
+                    // (tile origins are even: the parities of ts = t0 + ht - 1 and fs = f0 + hf - 1 are those of ht + 1 and hf + 1)
+                    const int ht_ = (e >> 3) / XH_HF, hf_ = (e >> 3) - ht_ * XH_HF;
+                    const unsigned sub = SLIM ? (unsigned)((((hf_ + 1) & 1) << 1) | ((ht_ + 1) & 1)) : hm[SLIM ? 0 : i] >> 1;
                     v.x = (ok && ha[i].x == sub) ? v.x : 0.f;
                     v.y = (ok && ha[i].y == sub) ? v.y : 0.f;
                     v.z = (ok && ha[i].z == sub) ? v.z : 0.f;
@@ -1207,14 +1257,18 @@ void conv3x3_x3h_kernel(ConvX3P p) {
     // fragment per lane covers all 32 k of a chunk (lane = row (lane & 15), k-quarter (lane >> 4)).  Under the package power limit the chip
     // sustains 9-12 % more LDS-fed matrix work in this shape than in 32 x 32 x 16 (tools/probe/mfma_shape.py): half the accumulator traffic
     // per flop.  A tile's 4 registers are 4 consecutive tile rows = one pooling window, like a register group of the 32 x 32 layout.
-    // (conv5's data gradient -- 64 output channels, 16 x 16 pixel tiles, no un-pooling -- measured 4 % slower in this form: it keeps 32 x 32 x 16)
-    constexpr bool M16 = X3H_M16 != 0 && !(BN == 64 && G == 2 && WN == 2 && EPI == EPI_DGRAD && !UNPOOL);
+    // (conv5's data gradient -- 64 output channels, 16 x 16 pixel tiles, no un-pooling -- measured 4 % slower in this form with 32-channel waves
+    // and keeps 32 x 32 x 16; with 64-channel waves this form is the faster one, X3H_DG5)
+    constexpr bool M16 = X3H_M16 != 0 && !(BN == 64 && G == 2 && (WN == 2 || X3H_DG5 != 2) && EPI == EPI_DGRAD && !UNPOOL);
     constexpr int TM16 = WTM / 16, TN16 = WTN / 16;
+    // WN = 1 data-gradient epilogue: accumulator groups per batch of gate loads.  16 x 16 x 32: one 16-pixel row block (2 groups x 8 registers, two
+    // batches live; 4 groups spill 80-96 bytes); 32 x 32 x 16: one group of 4 registers (2 groups: 16 bytes of scratch, 4: 80)
+    constexpr int DGB16 = 2, DGB32 = 1;
     f32x16 acc[M16 ? 1 : TM][M16 ? 1 : TN];
     f32x4 acc4[M16 ? TM16 : 1][M16 ? TN16 : 1];
     const int l15 = lane & 15, q4 = lane >> 4;
     float inv = 1.f, mx = 0.f;                                 // NP = 2: 1 / (activation scale x weight scale); running bound of max|y|
-    if (NP == 2) inv = 1.f / (pow2_scale(amax_read(p.amax_in)) * *reinterpret_cast<const float*>(p.w3 + (long)NP * nk * Cout * 64));
+    if (NP == 2) inv = 1.f / (pow2_scale(x3_amax_read<SLIM>(p.amax_in)) * *reinterpret_cast<const float*>(p.w3 + (long)NP * nk * Cout * 64));
     int cur_task = 0;                                          // (several tasks per launch: the task of the tile being finished)
     X3Cur cur_epi;
     const float* bias_t = p.bias;
@@ -1234,7 +1288,7 @@ void conv3x3_x3h_kernel(ConvX3P p) {
             for (int jn = 0; jn < TN; ++jn)
                 for (int nt = 0; nt < p.ntile; ++nt) bmax = fmaxf(bmax, fabsf(bias_t[nt * BN + wn * WTN + jn * 32 + l31]));
         }
-        amax_raise(p.amax_out + cur_task * p.sAmaxOut, mx + bmax);
+        x3_amax_raise<SLIM>(p.amax_out + cur_task * p.sAmaxOut, mx + bmax);
     };
     int abase[TM];                                             // byte offset of this lane's pixel (tap centre) in the halo plane
 #pragma unroll
@@ -1354,7 +1408,7 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                         cur_task = tk;
                         bias_t = p.bias + tk * p.sBias;
                         if (NP == 2)
-                            inv = 1.f / (pow2_scale(amax_read(p.amax_in + tk * p.sAmaxIn)) *
+                            inv = 1.f / (pow2_scale(x3_amax_read<SLIM>(p.amax_in + tk * p.sAmaxIn)) *
                                          *reinterpret_cast<const float*>(p.w3 + tk * p.sW + (long)NP * nk * Cout * 64));
                     }
                 }
@@ -1394,6 +1448,111 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                     walk(EpiConvRelu{p.y, bias_t, tl.b, ts0, tl.f0, T, F, Cout, n0});
                 } else if (EPI == EPI_POOL) {
                     walk(EpiConvPool{p.y, p.am_out, bias_t, tl.b, ts0, tl.f0, Tp, Fp, Cout, n0});
+                } else if constexpr (WN == 1 && EPI == EPI_DGRAD) {
+                    // 64 px x 64 ch wave tiles under 128 registers: 64 accumulators leave no room for all 64 gate values and a 64-bit address
+                    // per load and store.  (a) Addresses: everything but the lane's own column / frequency term is wave-uniform (the tile,
+                    // the wave's rows, the accumulator group), so every access is a scalar base + ONE 32-bit lane offset, and the lane terms
+                    // come from an opaque copy of the lane index -- kept from the prologue they would be spilled across the matrix loop, like
+                    // the tile's (above).  (b) Gate values: in batches of GB accumulator groups, batch k + 1 requested before batch k is
+                    // stored (act and dx may alias as far as the compiler knows, so no load moves above the stores of batch k - 1): one
+                    // batch of loads in flight under the other's stores, 2 x 16 gate registers.  Per element the arithmetic and the
+                    // addresses are those of EpiConvDgrad::gate4* / store4*g.
+                    int el;
+                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el));
+                    const int sb = __builtin_amdgcn_readfirstlane(tl.b), sf0 = __builtin_amdgcn_readfirstlane(tl.f0);
+                    const int st0 = __builtin_amdgcn_readfirstlane(ts0 + 4 * wm), sn0 = __builtin_amdgcn_readfirstlane(n0);
+                    // rows of the wave's group at 32-row block ib: t = st0 + 2 ib + (j & 1); f = sf0 + fu + fl (fu: group and j, fl: lane)
+                    auto gate_base = [&](int t, int cb) {          // clamped row, columns from cb
+                        return reinterpret_cast<const char*>(p.act + ((((long)sb * T + min(t, T - 1)) * F + sf0) * Cout + sn0 + cb));
+                    };
+                    auto out_base = [&](int t, int fu, int cb) {
+                        return reinterpret_cast<char*>(p.y + ((((long)sb * T + t) * F + sf0 + fu) * Cout + sn0 + cb));
+                    };
+                    if constexpr (M16) {
+                        constexpr int NG = TM16 * (TN16 / 2);                     // groups: 4 rows x one channel pair of a 32-channel block
+                        constexpr int GB = DGB16, NB = NG / GB;                   // groups per batch
+                        static_assert(NG % GB == 0, "whole batches");
+                        const int fl = 2 * (el >> 4);
+                        const unsigned lcol = 2 * (el & 15);
+                        const unsigned so = (unsigned)(fl * Cout + lcol) * 4u;
+                        f32x2v gate16[NB > 1 ? 2 : 1][GB][4];
+                        auto load_gates = [&](int bt) {
+#pragma unroll
+                            for (int e = 0; e < GB; ++e) {
+                                const int u = bt * GB + e, i = u / (TN16 / 2), jp = u % (TN16 / 2);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const int fc = min(sf0 + 8 * (i & 1) + (k >> 1) + fl, F - 1) - sf0;
+                                    gate16[bt & 1][e][k] = __builtin_nontemporal_load(reinterpret_cast<const f32x2v*>(
+                                        gate_base(st0 + 2 * (i >> 1) + (k & 1), jp * 32) + (unsigned)(fc * Cout + lcol) * 4u));
+                                }
+                            }
+                        };
+                        load_gates(0);
+#pragma unroll
+                        for (int bt = 0; bt < NB; ++bt) {
+                            if (bt + 1 < NB) load_gates(bt + 1);
+#pragma unroll
+                            for (int e = 0; e < GB; ++e) {
+                                const int u = bt * GB + e, i = u / (TN16 / 2), jp = u % (TN16 / 2);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const float v0 = NP == 2 ? acc4[i][2 * jp][k] * inv : acc4[i][2 * jp][k];
+                                    const float v1 = NP == 2 ? acc4[i][2 * jp + 1][k] * inv : acc4[i][2 * jp + 1][k];
+                                    mx = fmaxf(mx, fmaxf(fabsf(v0), fabsf(v1)));
+                                    asm volatile("" : "+v"(mx));      // (pinned: sunk to the end of the epilogue the maxima keep every scaled value live)
+                                    const int t = st0 + 2 * (i >> 1) + (k & 1), fu = 8 * (i & 1) + (k >> 1);
+                                    const f32x2v m = gate16[bt & 1][e][k];
+                                    const f32x2v o = {m.x > 0.f ? v0 : 0.f, m.y > 0.f ? v1 : 0.f};
+                                    if (t < T && sf0 + fu + fl < F)
+                                        __builtin_nontemporal_store(o, reinterpret_cast<f32x2v*>(out_base(t, fu, jp * 32) + so));
+                                }
+                            }
+                        }
+                    } else {
+                        constexpr int NG = TM * TN * 4;                           // groups: 4 rows x one channel of a 32 x 32 tile
+                        constexpr int GB = DGB32, NB = NG / GB;
+                        static_assert(NG % GB == 0, "whole batches");
+                        const int fl = 2 * (el >> 5);
+                        const unsigned lcol = el & 31;
+                        const unsigned so = (unsigned)(fl * Cout + lcol) * 4u;
+                        float gate[NB > 1 ? 2 : 1][GB][4];
+                        auto load_gates = [&](int bt) {
+#pragma unroll
+                            for (int e = 0; e < GB; ++e) {
+                                const int u = bt * GB + e, i = u / (TN * 4), jn = (u >> 2) % TN, g = u & 3;
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const int fc = min(sf0 + 4 * g + (k >> 1) + fl, F - 1) - sf0;
+                                    gate[bt & 1][e][k] = __builtin_nontemporal_load(reinterpret_cast<const float*>(
+                                        gate_base(st0 + 2 * i + (k & 1), jn * 32) + (unsigned)(fc * Cout + lcol) * 4u));
+                                }
+                            }
+                        };
+                        load_gates(0);
+#pragma unroll
+                        for (int bt = 0; bt < NB; ++bt) {
+                            if (bt + 1 < NB) load_gates(bt + 1);
+#pragma unroll
+                            for (int e = 0; e < GB; ++e) {
+                                const int u = bt * GB + e, i = u / (TN * 4), jn = (u >> 2) % TN, g = u & 3;
+                                float v[4] = {acc[i][jn][4 * g], acc[i][jn][4 * g + 1], acc[i][jn][4 * g + 2], acc[i][jn][4 * g + 3]};
+                                if (NP == 2) {
+#pragma unroll
+                                    for (int k = 0; k < 4; ++k) v[k] *= inv;
+                                }
+                                mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                                asm volatile("" : "+v"(mx));
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const int t = st0 + 2 * i + (k & 1), fu = 4 * g + (k >> 1);
+                                    if (t < T && sf0 + fu + fl < F)
+                                        __builtin_nontemporal_store(gate[bt & 1][e][k] > 0.f ? v[k] : 0.f,
+                                                                    reinterpret_cast<float*>(out_base(t, fu, jn * 32) + so));
+                                }
+                            }
+                        }
+                    }
                 } else {
                     const EpiConvDgrad epi{p.y, p.act, tl.b, ts0, tl.f0, T, F, Cout, n0};
                     if (M16) {
@@ -1485,10 +1644,18 @@ int dispatch_conv_x3(ConvX3P& p, int Te, int Fe, hipStream_t s) {
         return launch_conv_x3h<128, 2, UNPOOL, EPI, NP>(p, Te, Fe, s);
     }
     p.ntile = p.g.Cout / 64;
-    // two-piece fp16 forward, 64 output channels: 16 x 16 tiles with FOUR consumer waves of 64 px x 64 ch, two workgroups per CU
-    // (LDS-bound with 32-channel waves, see the kernel's header: conv2 forward 0.385 -> 0.341 ms); the data-gradient epilogue does not
-    // fit the 128-VGPR budget of that shape (spills: 0.45 -> 0.71 ms)
+    // two-piece fp16, 64 output channels: 16 x 16 tiles with FOUR consumer waves of 64 px x 64 ch, two workgroups per CU (LDS-bound with
+    // 32-channel waves, see the kernel's header).  Forward: conv2 0.385 -> 0.341 ms.  Data gradients (8-task launches): conv2's (un-pooling
+    // source, 64 reduction channels) 2.93 -> 2.46 ms, conv5's (dense, 128) 1.33 -> 1.24 ms, both bit for bit what the 32-channel waves
+    // gave; their gated epilogue fits the 128 registers of this shape in the SLIM form of the kernel (before: spills, 0.45 -> 0.71 ms).
+    // 8 x 16 tiles with two 64 x 64 waves (G = 1, WN = 1) measured 3.47 ms on conv2's.  The other two classes keep their routes (not measured).
     if constexpr (NP == 2 && EPI != EPI_DGRAD) return launch_conv_x3h<64, 2, UNPOOL, EPI, NP, 1>(p, Te, Fe, s);
+    if constexpr (NP == 2 && UNPOOL && X3H_DG2 != 0) {         // (the SLIM halo fetch addresses a pooled sample with 32-bit byte offsets)
+        if (p.g.Cin == 64 && (long)p.g.Tp * p.g.Fp * p.g.Cin < (1L << 30)) return launch_conv_x3h<64, 2, UNPOOL, EPI, NP, 1>(p, Te, Fe, s);
+    }
+    if constexpr (NP == 2 && !UNPOOL && X3H_DG5 != 0) {
+        if (p.g.Cin != 64) return launch_conv_x3h<64, 2, UNPOOL, EPI, NP, 1>(p, Te, Fe, s);
+    }
     if (p.g.Cin == 64) return launch_conv_x3h<64, 1, UNPOOL, EPI, NP>(p, Te, Fe, s);
     return launch_conv_x3h<64, 2, UNPOOL, EPI, NP>(p, Te, Fe, s);
 }
