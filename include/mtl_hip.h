@@ -301,7 +301,8 @@ typedef struct mtl_ln_reduce_desc {
 int mtl_ln_param_reduce_batch(void* stream, const mtl_ln_reduce_desc* table_dev, int n, int dmax);
 
 /* ---- masked softmax: modules/common_layers.py:322-327.  S is [B][H][Tq][ld], in place.
- * keys k >= klen[b] (klen nullable) and, if causal, k > q are filled with -inf before the softmax. */
+ * keys k >= klen[b] (klen nullable) and, if causal, k > q are filled with -inf before the softmax.
+ * A row without a live key (klen[b] <= 0) becomes all zeros, not the NaN torch.softmax gives for an all -inf row; its backward is zero too. */
 /* pmask (nullable u8 keep-mask, same [B][H][Tq][ld] layout) / pscale: dropout on the probabilities (common_layers.py:328);
  * P stays un-dropped in S (needed by the backward), the dropped copy that feeds P.V is written to P_dropped. */
 int mtl_softmax_mask_fwd(void* stream, float* S, const int* klen, int causal, float scale, int B, int H, int Tq, int Tk,

@@ -445,6 +445,9 @@ def test_layernorm(L, d):
     (8, 8, 1, 301, 64, 0, [1, 2, 64, 65, 150, 256, 257, 301], 0.0),     # ONE query row per (batch, head): the decode kernel over a K/V cache
     (3, 8, 1, 250, 64, 0, None, 0.0),                 # ... cross-attention of a decoding step: every key
     (2, 8, 1, 40, 16, 0, [40, 7], 0.0),               # ... fixture head size
+    (2, 8, 128, 128, 64, 1, [128, 64], 0.0),          # lengths that are exact multiples of the 64-row tile: causal, two tiles
+    (2, 8, 64, 128, 64, 0, [128, 64], 0.0),           # ... one query tile against two key tiles, a key length on the tile edge
+    (1, 8, 64, 64, 16, 1, None, 0.0),                 # ... one tile, fixture head size
 ])
 def test_fused_attention_forward_and_backward(L, B, H, Tq, Tk, dk, causal, klens, drop):
     """mtl_attn_fwd / mtl_attn_bwd against ScaledDotProductAttention written out in torch (modules/common_layers.py:317-331:
