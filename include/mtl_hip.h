@@ -452,6 +452,21 @@ int mtl_tempo_search(void* stream, const float* wav, const long* offsets, const 
  *     cannot read out of bounds.  out has sum of N_k floats. */
 int mtl_tempo_render(void* stream, const float* wav, const long* offsets, const long* out_offsets, const double* tempo, const float* gain,
                      const long* seg_base, const int* seg_off, int K, int seg, int search, int overlap, int quantize, float* out);
+/* Sample-rate conversion on the device (audio_with_sox / augment_audio_with_sox, utils/audio.py: `sox -r`), in front of the tempo calls
+ * (csrc/mtl_resample.hip).  sox is not reproduced sample for sample: the behaviour is DEFINED here and in DESIGN.md section 14, parity
+ * unpinned.  wav / offsets as in mtl_spect_batch (utterance k: L_k samples, read as 0 outside [0, L_k)); out_offsets: K + 1 int64, the
+ * converted utterance k has N_k = out_offsets[k+1] - out_offsets[k] samples (the caller's N_k = ceil(L_k up_k / down_k)).
+ *   plan: 4 int64 per utterance: up_k, down_k, half_k and base_k, its filter being taps[base_k .. base_k + 2 half_k] (n_taps doubles in
+ *   all, the filters of the distinct ratios one after the other; formed by the caller in fp64 and used as uploaded).
+ *   out[out_offsets[k] + j] = sum_i x[i] taps[base_k + j down_k - i up_k + half_k] over 0 <= i < L_k with the tap index in
+ *   [0, 2 half_k]: fp64, one fma per term, ascending i; j down_k and every offset are 64-bit.  up_k == down_k copies the utterance bit
+ *   for bit.  quantize != 0: every converted sample y then becomes clip(rint(y 32768), -32768, 32767) / 32768, formed in fp64 (the
+ *   16-bit file without dither; the copies of the bypass are left alone); quantize == 0: (float)y.
+ *   Every sample and tap read is bounded by the tables' own ranges; a plan with up or down outside [1, 1024] or a filter outside
+ *   [0, n_taps) reads nothing and writes zeros.  1 <= K <= 2^20, n_taps >= 1; null pointers and anything else return -22 before any
+ *   launch.  One launch, no workspace, no atomics: bitwise repeatable.  out has sum of N_k floats. */
+int mtl_resample(void* stream, const float* wav, const long* offsets, const long* out_offsets, const long* plan, const double* taps,
+                 long n_taps, int K, int quantize, float* out);
 
 /* ---- accent discriminator on the encoder output (joint_train.py --multitask / --adversarial) ------------------------------
  * modules/discriminator.py, trainer/asr/joint_trainer.py:29-37, utils/metrics.py:164-199 (csrc/mtl_disc.hip):

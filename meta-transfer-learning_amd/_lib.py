@@ -119,6 +119,7 @@ SIGNATURES = {
     'mtl_spect_batch_noise': (I, [P, P, P, I, I, I, P, I, I, P, I, I, P, L, P, L, P, P]),
     'mtl_tempo_search': (I, [P, P, P, P, P, P, I, I, I, I, P]),
     'mtl_tempo_render': (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
+    'mtl_resample': (I, [P, P, P, P, P, P, L, I, I, P]),
     'mtl_disc_workspace': (L, [I, I, I]),
     'mtl_disc_fwd': (I, [P, P, I, I, I, P, P, I, I, I, P, P, P, P, L]),
     'mtl_disc_bwd': (I, [P, P, P, P, I, I, I, I, I, I, F, F, P, P, P]),

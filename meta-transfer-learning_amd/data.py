@@ -138,7 +138,7 @@ class ManifestTaskDataset:
     `__getitem__` / `__len__` follow utils/data_loader.py:323-340 (validation / test use: manifest 0 only unless is_train)."""
 
     def __init__(self, vocab, args, manifest_filepath_list, feature_fn=None, partitions=None, seed=None, is_train=False,
-                 device_batches=False, noise=None, augment=None):
+                 device_batches=False, noise=None, augment=None, resample=False):
         """device_batches=True: `sample()` featurises each part (train / validation) with ONE `SpectrogramFrontEnd.batch` call and
         returns `inputs` on the device (the trainers copy device-resident inputs straight into their static buffers); the sizes,
         percentages and targets stay host tensors as `collate` makes them, and the index stream is the same.  The front-end is
@@ -155,7 +155,15 @@ class ManifestTaskDataset:
         tempo, then a random gain, then the 16-bit file) before anything else happens to it, on the device, in the batched path only
         (device_batches=True; not with a feature_fn).  Per utterance the stream yields tempo, gain and THEN that utterance's noise
         draws, as parse_audio interleaves them (utils/data_loader.py:67-75); the noise segment is as long as the STRETCHED utterance.
-        A part that `need` leaves out consumes these draws too.  augment=None leaves the stream exactly as it is without."""
+        A part that `need` leaves out consumes these draws too.  augment=None leaves the stream exactly as it is without.
+
+        resample=True: the sample rate in every wav header is read (`load_wav_pcm16_rate`) and an utterance at another rate than
+        args.sample_rate is converted on the device before anything else happens to it (`SpectrogramFrontEnd.batch(rates=)`, `resample`
+        for the definition): corpora at 8 kHz and at 16 kHz train together without an offline pass.  The batched path hands the rates
+        of a part to its one `batch` call; the per-utterance path (`__getitem__`, the rows of `sample()` without device_batches) sends
+        an utterance whose rate differs through `batch([y], rates=[rate])`.  The augmentation and noise plans are made for the
+        CONVERTED lengths; no draw is added, so the stream is the same with and without.  Not with a feature_fn (which gets paths).
+        resample=False (the default) never reads the header rate: every call and every output bit is as without the keyword."""
         if device_batches and feature_fn is not None:
             raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
         if noise is not None and feature_fn is not None:
@@ -164,6 +172,9 @@ class ManifestTaskDataset:
             raise NotImplementedError('tempo / gain augmentation runs on the device: it cannot be combined with a feature_fn (which gets paths)')
         if augment is not None and not device_batches:
             raise NotImplementedError('tempo / gain augmentation exists in the batched device path only: pass device_batches=True')
+        if resample and feature_fn is not None:
+            raise NotImplementedError('sample rates are converted on the device: resample=True cannot be combined with a feature_fn (which gets paths)')
+        self._resample, self._rate = bool(resample), getattr(args, 'sample_rate', None)     # (a feature_fn needs no rate)
         self._noise = None if noise is None else (noise[0], float(noise[1]))
         self._augment = augment
         self.device_batches, self._fe = device_batches, None
@@ -206,10 +217,19 @@ class ManifestTaskDataset:
         """per-utterance path: feature_fn(path), or for an utterance whose draw = (augmentation, noise) asks for either
         `batch([y], augment=..., noise=...)[0][0, 0]`, handed back on the host like every feature; an utterance that `place` leaves clean
         (longer than its noise file) and is not augmented takes the clean path"""
-        if draw is None or (draw[0] is None and draw[1] is None):
+        rate = None
+        if self._resample:                                       # (a file at the front-end's own rate takes the paths below as it is)
+            y, rate = load_wav_pcm16_rate(path)
+            rate = None if rate == self._rate else rate
+        if draw is None:
+            draw = (None, None)
+        if rate is None and draw[0] is None and draw[1] is None:
             return self.feature_fn(path)
-        y = load_wav_pcm16(path)
+        if not self._resample:
+            y = load_wav_pcm16(path)
         kw, n = {}, y.shape[0]
+        if rate is not None:
+            kw['rates'], n = [rate], int(resample_plan([n], [rate], self._rate)[0][0])
         if draw[0] is not None:
             tempo, gain_db, out_lengths = self._augment.plan([draw[0]], [n])
             kw['augment'], n = (tempo, gain_db), int(out_lengths[0])
@@ -240,9 +260,15 @@ class ManifestTaskDataset:
         """one part of a sampled batch through SpectrogramFrontEnd.batch: the 5-tuple of `collate` with `inputs` on the device
         (draws: one augmentation `plan` and one noise `plan` -- on the stretched lengths -- for the part; the noisy form of the call
         unless every utterance stays clean)"""
-        waves = [load_wav_pcm16(ids[j][0]) for j in picks]
+        if self._resample:
+            waves, rates = zip(*[load_wav_pcm16_rate(ids[j][0]) for j in picks])
+            waves = list(waves)
+        else:
+            waves = [load_wav_pcm16(ids[j][0]) for j in picks]
         trans = [parse_transcript(self.vocab, ids[j][1]) for j in picks]
         kw, lengths = {}, [w.shape[0] for w in waves]
+        if self._resample:                                       # the plans below are made for the converted lengths
+            kw['rates'], lengths = list(rates), resample_plan(lengths, rates, self._rate)[0]
         if draws is not None and self._augment is not None:
             tempo, gain_db, lengths = self._augment.plan([d[0] for d in draws], lengths)
             kw['augment'] = (tempo, gain_db)
@@ -312,10 +338,15 @@ class SpectrogramDataset(ManifestTaskDataset):
     for the draw stream and TempoGainAugment for the semantics (a restatement of ours: sox is not reproduced sample for sample).
     Outside the accelerated path and rejected loudly: input_type other than 'char' (the bpe / ipa branches are commented out in the
     reference too).
-    device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off)."""
+    device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off).
+    resample=True: files at another rate than audio_conf['sample_rate'] are converted on the device, see ManifestTaskDataset (not part of the
+    reference's constructor either, which leaves this to sox; default off, and then the header rate is never read)."""
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
-                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False):
+                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False):
+        if resample and feature_fn is not None:
+            raise NotImplementedError('sample rates are converted on the device: resample=True cannot be combined with a feature_fn (which '
+                                      'gets paths)')
         if device_batches and feature_fn is not None:
             raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
         if augment and feature_fn is not None:
@@ -352,6 +383,7 @@ class SpectrogramDataset(ManifestTaskDataset):
         super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
         self._noise = noise                                          # (after the base constructor: the default feature_fn is no user's)
         self._augment = TempoGainAugment() if augment else None
+        self._resample, self._rate = bool(resample), self.sample_rate
         self.device_batches, self._fe_factory = device_batches, front_end       # (sample() of a part: one front_end().batch call)
         self.manifest_filepath_list, self.input_type = manifest_filepath_list, input_type
         # (the reference leaves part_len at the LAST manifest's partition size, or max_size without partitions: :211-222)
@@ -461,6 +493,14 @@ def load_wav_pcm16(path):
     return raw.reshape(-1, ch).mean(axis=1).astype(np.float32) if ch > 1 else raw
 
 
+def load_wav_pcm16_rate(path):
+    """(load_wav_pcm16(path), the sample rate in the file's header): what a front-end that converts rates needs (`resample`)"""
+    import wave
+    with wave.open(path, 'rb') as w:
+        rate = w.getframerate()
+    return load_wav_pcm16(path), int(rate)
+
+
 def pack_waveforms(waves, hop, n_fft, max_frames=None):
     """K one-dimensional waveforms -> (flat float32 (sum of L_k), offsets int64 (K + 1), frames int32 (K), Tmax): the host side of
     `SpectrogramFrontEnd.batch`, pure numpy.  frames[k] = min(1 + L_k // hop, max_frames), Tmax = max(frames).  An utterance shorter
@@ -550,7 +590,15 @@ def tempo_gain_tables(waves, tempo, gain_db, sample_rate):
         if a.ndim != 1:
             raise ValueError('tempo_gain_tables: waveform %d is not one-dimensional (shape %s)' % (i, a.shape))
         arrs.append(a)
-    K = len(arrs)
+    tab = _tempo_gain_plan([a.shape[0] for a in arrs], tempo, gain_db, sample_rate)
+    tab['flat'] = np.concatenate(arrs)
+    return tab
+
+
+def _tempo_gain_plan(lengths, tempo, gain_db, sample_rate):
+    """`tempo_gain_tables` without the samples, from the K lengths alone (the lengths after a rate conversion are known on the host, the
+    samples exist on the device only)"""
+    K = len(lengths)
     tempo = np.ascontiguousarray(tempo, dtype=np.float64)
     gain_db = np.ascontiguousarray(gain_db, dtype=np.float32)
     if tempo.shape != (K,) or gain_db.shape != (K,):
@@ -560,15 +608,14 @@ def tempo_gain_tables(waves, tempo, gain_db, sample_rate):
         raise ValueError('tempo_gain_tables: a search of %d or an overlap of %d samples (sample rate %s) is beyond the 256 the kernel covers'
                          % (R, O, sample_rate))
     H = S - O
-    lengths = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+    lengths = np.array(lengths, dtype=np.int64)
     out_lengths = np.array([TempoGainAugment.out_length(n, t) for n, t in zip(lengths, tempo)], dtype=np.int64)
     offsets, out_offsets, seg_base = (np.zeros(K + 1, dtype=np.int64) for _ in range(3))
     np.cumsum(lengths, out=offsets[1:])
     np.cumsum(out_lengths, out=out_offsets[1:])
     np.cumsum(np.where(tempo == 1.0, 0, (out_lengths + H - 1) // H), out=seg_base[1:])
     gain = (10.0 ** (gain_db.astype(np.float64) / 20.0)).astype(np.float32)
-    return dict(flat=np.concatenate(arrs), offsets=offsets, out_offsets=out_offsets, seg_base=seg_base, tempo=tempo, gain=gain,
-                geometry=(S, R, O))
+    return dict(offsets=offsets, out_offsets=out_offsets, seg_base=seg_base, tempo=tempo, gain=gain, geometry=(S, R, O))
 
 
 def _tempo_gain_launch(lib, stream, tab, d_wav, d_off, d_ooff, d_sbase, d_tempo, d_gain, quantize, device):
@@ -613,6 +660,121 @@ def load_randomly_augmented_audio(path, sample_rate=16000, tempo_range=(0.85, 1.
     return tempo_gain([load_wav_pcm16(path)], [tempo], [gain_db], sample_rate)[0][0]
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Sample-rate conversion on the device (audio_with_sox / augment_audio_with_sox, utils/audio.py: `sox -r`); DESIGN.md section 14
+# ------------------------------------------------------------------------------------------------------------------
+RESAMPLE_MAX_RATIO = 1024
+_RESAMPLE_TAPS = {}           # (up, down) -> the fp64 filter of `resample_taps` with its defaults (read-only arrays)
+
+
+def resample_plan(lengths, rates, sample_rate):
+    """K lengths and the K rates of their files -> (out_lengths, up, down), int64 (K) each: g = gcd(rate, sample_rate), up = sample_rate / g,
+    down = rate / g, N = ceil(L up / down) in integers.  rate == sample_rate is the bypass (up = down = 1, N = L).  A ratio with
+    max(up, down) > 1024 (44101 Hz to 16 kHz, say) raises ValueError: such a filter would have more than 32 k taps."""
+    import math
+    lengths = np.array(lengths, dtype=np.int64).reshape(-1)
+    rates = np.array(rates).reshape(-1)
+    if rates.shape != lengths.shape:
+        raise ValueError('resample_plan: %d rates for %d waveforms' % (rates.shape[0], lengths.shape[0]))
+    target = int(sample_rate)
+    if target != sample_rate or target < 1:
+        raise ValueError('resample_plan: the target rate must be a positive integer, got %r' % (sample_rate,))
+    up, down = np.ones(len(lengths), dtype=np.int64), np.ones(len(lengths), dtype=np.int64)
+    for k, r in enumerate(rates):
+        if int(r) != r or int(r) < 1:
+            raise ValueError('resample_plan: the rate of waveform %d must be a positive integer, got %r' % (k, r))
+        g = math.gcd(int(r), target)
+        up[k], down[k] = target // g, int(r) // g
+        if max(up[k], down[k]) > RESAMPLE_MAX_RATIO:
+            raise ValueError('resample_plan: %d Hz to %d Hz is the ratio %d / %d, beyond the %d that the conversion covers'
+                             % (int(r), target, up[k], down[k], RESAMPLE_MAX_RATIO))
+    return (lengths * up + down - 1) // down, up, down
+
+
+def resample_taps(up, down, zeros=16, beta=8.6, rolloff=0.95):
+    """the filter of the ratio up / down in fp64, 2 half + 1 taps: q = max(up, down), half = zeros q, n = -half .. half, fc = rolloff / q,
+    h = fc sinc(fc n) kaiser(2 half + 1, beta), scaled so that sum(h) == up (unit gain at 0 Hz after the zero stuffing): `zeros` zero
+    crossings of the sinc on either side, the cutoff at `rolloff` of the lower Nyquist frequency"""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError('resample_taps: up and down must be positive, got %d / %d' % (up, down))
+    q = max(up, down)
+    half = int(zeros) * q
+    n = np.arange(-half, half + 1, dtype=np.float64)
+    fc = float(rolloff) / q
+    h = fc * np.sinc(fc * n) * np.kaiser(2 * half + 1, beta)
+    return h * (up / h.sum())
+
+
+def resample_tables(waves, rates, sample_rate):
+    """host side of the rate conversion, pure numpy: dict(flat float32 (sum of L_k), offsets int64 (K + 1), out_offsets int64 (K + 1) from
+    `resample_plan`, plan int64 (K, 4): up, down, half and the base of the utterance's filter in taps, taps float64: the filters of the
+    DISTINCT ratios of this call one after the other (a bypassed utterance has none: half = base = 0; never empty).  The filters are
+    formed once per (up, down) and kept."""
+    if len(waves) == 0:
+        raise ValueError('resample_tables: an empty list of waveforms')
+    arrs = []
+    for i, w in enumerate(waves):
+        a = np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError('resample_tables: waveform %d is not one-dimensional (shape %s)' % (i, a.shape))
+        arrs.append(a)
+    K = len(arrs)
+    lengths = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+    out_lengths, up, down = resample_plan(lengths, rates, sample_rate)
+    offsets, out_offsets = np.zeros(K + 1, dtype=np.int64), np.zeros(K + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    np.cumsum(out_lengths, out=out_offsets[1:])
+    plan, base, filters, total = np.zeros((K, 4), dtype=np.int64), {}, [], 0
+    for k in range(K):
+        key = (int(up[k]), int(down[k]))
+        plan[k, 0], plan[k, 1] = key
+        if key[0] == key[1]:
+            continue
+        if key not in _RESAMPLE_TAPS:
+            h = resample_taps(*key)
+            h.setflags(write=False)
+            _RESAMPLE_TAPS[key] = h
+        if key not in base:
+            base[key] = total
+            filters.append(_RESAMPLE_TAPS[key])
+            total += filters[-1].shape[0]
+        plan[k, 2], plan[k, 3] = (_RESAMPLE_TAPS[key].shape[0] - 1) // 2, base[key]
+    taps = np.concatenate(filters) if filters else np.zeros(1, dtype=np.float64)
+    return dict(flat=np.concatenate(arrs), offsets=offsets, out_offsets=out_offsets, plan=plan, taps=taps)
+
+
+def _resample_launch(lib, stream, tab, d_wav, d_off, d_ooff, d_plan, d_taps, quantize, device):
+    """mtl_resample on `stream` (operands on the device, output allocated with the current stream) -> the converted packed waveforms"""
+    from . import _lib
+    total = int(tab['out_offsets'][-1])
+    out = torch.empty(max(total, 1), dtype=torch.float32, device=device)
+    _lib.check(lib.mtl_resample(stream, d_wav.data_ptr(), d_off.data_ptr(), d_ooff.data_ptr(), d_plan.data_ptr(), d_taps.data_ptr(),
+                                tab['taps'].shape[0], tab['plan'].shape[0], 1 if quantize else 0, out.data_ptr()), 'mtl_resample')
+    return out[:total]
+
+
+def resample(waves, rates, sample_rate=16000, quantize=True, device='cuda'):
+    """K waveforms sampled at rates[k] converted to `sample_rate` on the device -> list of K float32 numpy arrays of
+    ceil(L_k up_k / down_k) samples (`resample_plan`, `resample_taps` and DESIGN.md section 14 for the definition: a zero-phase
+    Kaiser-windowed sinc with zero extension, fp64 sums; sox is not reproduced sample for sample).  quantize=True rounds to the 16-bit
+    file that audio_with_sox leaves (without sox's dither), quantize=False returns the sums rounded once to fp32.  An utterance that is at
+    `sample_rate` already is copied bit for bit either way.  The unfused form of `SpectrogramFrontEnd.batch(rates=)`, on the current stream."""
+    from . import _lib
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('sample rates are converted on the MI355X only (no CPU fallback)')
+    tab = resample_tables(waves, rates, sample_rate)
+    lib = _lib.lib()
+    d = {k: torch.from_numpy(tab[k]).to(dev) for k in ('flat', 'offsets', 'out_offsets', 'plan', 'taps')}
+    if d['flat'].numel() == 0:
+        d['flat'] = torch.zeros(1, device=dev)
+    out = _resample_launch(lib, torch.cuda.current_stream(dev).cuda_stream, tab, d['flat'], d['offsets'], d['out_offsets'], d['plan'],
+                           d['taps'], quantize, dev)
+    out, oo = out.cpu().numpy(), tab['out_offsets']
+    return [out[oo[k]:oo[k + 1]].copy() for k in range(len(waves))]
+
+
 class SpectrogramFrontEnd:
     """wav -> STFT (n_fft = win = sample_rate*window_size, hop = sample_rate*window_stride, symmetric Hamming window,
     center + reflect padding = librosa.stft defaults of the reference era) -> |.| -> log1p -> (x-mean)/std, all on the MI355X:
@@ -645,6 +807,7 @@ class SpectrogramFrontEnd:
         self._pin_wav = self._pin_off = None                   # pinned staging of batch(), grown on demand
         self._pin_noff = self._pin_lvl = None                  # ... and of its two noise tables
         self._pin_aug = self._pin_tempo = self._pin_gain = None # ... and of the augmentation tables
+        self._pin_rs = self._pin_taps = None                   # ... and of the rate conversion's tables
 
     def __call__(self, y):
         """y: 1-D float waveform (numpy or tensor) -> (F, T) fp32 tensor on the device, T = 1 + len(y) // hop."""
@@ -665,7 +828,7 @@ class SpectrogramFrontEnd:
                                         1 if self.normalize else 0), 'mtl_spect_logmag')
         return out
 
-    def batch(self, waves, max_frames=None, noise=None, augment=None):
+    def batch(self, waves, max_frames=None, noise=None, augment=None, rates=None):
         """K waveforms -> (inputs (K, 1, F, Tmax) fp32 on the device, input_sizes (K) int32 on the host): what `collate` builds from
         K `__call__` results cut to max_frames, in one device pass -- one pinned staging copy of the concatenated samples and of the
         offsets (two H2D copies) and the two launches of mtl_spect_batch (framing, STFT, log-magnitude, per-utterance statistics over
@@ -692,22 +855,41 @@ class SpectrogramFrontEnd:
         under the same event: the result is bitwise `batch(tempo_gain(waves, tempo, gain_db)[0], ...)`.  input_sizes, Tmax and the
         n_fft // 2 + 1 minimum of `pack_waveforms` refer to the stretched lengths, and a noise plan must have been made for them.  The
         offsets, the segment table's prefix, the factors and the gains travel through pinned staging like the noise tables.
-        augment=None issues exactly the calls described above."""
+        augment=None issues exactly the calls described above.
+
+        rates=K sample rates, those of the files that `waves` were read from (`load_wav_pcm16_rate`): utterance k is first converted
+        from rates[k] to this front-end's sample rate as `resample` does -- ONE more launch, mtl_resample, in front of the tempo stage,
+        into a packed buffer of the converted waveforms at new offsets -- and everything above (tempo and gain, noise, the STFT) runs
+        unchanged on that buffer at the target rate, on the same stream under the same event: the result is bitwise
+        `batch(resample(waves, rates, sample_rate), ...)` with the same other arguments.  (Conversion first is this project's choice: the
+        later stages are defined at the front-end's rate.  sox's own chain `tempo f gain g rate r` converts last.)  input_sizes, Tmax and
+        the n_fft // 2 + 1 minimum refer to the converted lengths (`resample_plan`), and the augmentation and noise plans must have been
+        made for them.  The original samples, the input offsets with the per-utterance plan and the filters travel through pinned
+        staging.  No random draw is involved.  An utterance that is at the target rate already is copied bit for bit.  rates=None
+        issues exactly the calls described above."""
         from . import _lib
         if self.device.type != 'cuda':
             raise RuntimeError('the spectrogram front-end runs on the MI355X only (no CPU fallback)')
         lib = _lib.lib()
-        aug = None
-        if augment is None:
+        aug = rs = None
+        if augment is None and rates is None:
             flat, offsets, frames, tmax = pack_waveforms(waves, self.hop, self.n_fft, max_frames)
         else:
-            # the samples that are uploaded are the original ones; everything downstream sees the stretched lengths
-            aug = tempo_gain_tables(waves, augment[0], augment[1], self.sample_rate)
-            flat, offsets = aug['flat'], aug['out_offsets']
+            # the samples that are uploaded are the original ones; everything downstream sees the converted / stretched lengths
+            if rates is not None:
+                rs = resample_tables(waves, rates, self.sample_rate)
+                flat, offsets = rs['flat'], rs['out_offsets']
+            if augment is not None and rs is None:
+                aug = tempo_gain_tables(waves, augment[0], augment[1], self.sample_rate)
+                flat, offsets = aug['flat'], aug['out_offsets']
+            elif augment is not None:
+                aug = _tempo_gain_plan(np.diff(rs['out_offsets']), augment[0], augment[1], self.sample_rate)
+                offsets = aug['out_offsets']
             short = np.flatnonzero(np.diff(offsets) < self.n_fft // 2 + 1)
             if short.size:
-                raise ValueError('batch: utterance %d has %d samples after the tempo change, fewer than n_fft // 2 + 1 = %d (one reflection '
-                                 'must suffice)' % (short[0], np.diff(offsets)[short[0]], self.n_fft // 2 + 1))
+                raise ValueError('batch: utterance %d has %d samples after the %s, fewer than n_fft // 2 + 1 = %d (one reflection '
+                                 'must suffice)' % (short[0], np.diff(offsets)[short[0]], 'rate conversion' if aug is None else 'tempo change',
+                                                    self.n_fft // 2 + 1))
             frames = 1 + np.diff(offsets) // self.hop
             if max_frames is not None:
                 frames = np.minimum(frames, max_frames)
@@ -753,6 +935,15 @@ class SpectrogramFrontEnd:
             self._pin_aug[K + 1:2 * (K + 1)].copy_(torch.from_numpy(aug['seg_base']))
             self._pin_tempo[:K].copy_(torch.from_numpy(aug['tempo']))
             self._pin_gain[:K].copy_(torch.from_numpy(aug['gain']))
+        if rs is not None:
+            n_taps = rs['taps'].shape[0]
+            if self._pin_rs is None or self._pin_rs.numel() < 5 * K + 1:
+                self._pin_rs = torch.empty(max(5 * K + 1, 128), dtype=torch.int64).pin_memory()
+            if self._pin_taps is None or self._pin_taps.numel() < n_taps:
+                self._pin_taps = torch.empty(max(n_taps, 1 << 12), dtype=torch.float64).pin_memory()
+            self._pin_rs[:K + 1].copy_(torch.from_numpy(rs['offsets']))
+            self._pin_rs[K + 1:5 * K + 1].copy_(torch.from_numpy(rs['plan'].reshape(-1)))
+            self._pin_taps[:n_taps].copy_(torch.from_numpy(rs['taps']))
         with torch.cuda.stream(self.stream):
             inputs = torch.empty(K, 1, self.F, tmax, device=self.device)
             d_wav = torch.empty(flat.shape[0], device=self.device)
@@ -760,6 +951,11 @@ class SpectrogramFrontEnd:
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
             d_wav.copy_(self._pin_wav[:flat.shape[0]], non_blocking=True)
             d_off.copy_(self._pin_off[:K + 1], non_blocking=True)
+            if rs is not None:
+                d_rs = torch.empty(5 * K + 1, dtype=torch.int64, device=self.device)
+                d_taps = torch.empty(n_taps, dtype=torch.float64, device=self.device)
+                d_rs.copy_(self._pin_rs[:5 * K + 1], non_blocking=True)
+                d_taps.copy_(self._pin_taps[:n_taps], non_blocking=True)
             if aug is not None:                                 # d_wav holds the original samples, d_off the STRETCHED offsets
                 d_aug = torch.empty(2 * (K + 1), dtype=torch.int64, device=self.device)
                 d_tempo = torch.empty(K, dtype=torch.float64, device=self.device)
@@ -767,6 +963,10 @@ class SpectrogramFrontEnd:
                 d_aug.copy_(self._pin_aug[:2 * (K + 1)], non_blocking=True)
                 d_tempo.copy_(self._pin_tempo[:K], non_blocking=True)
                 d_gain.copy_(self._pin_gain[:K], non_blocking=True)
+            if rs is not None:                                  # the converted offsets are the next stage's input offsets
+                d_wav = _resample_launch(lib, self.stream.cuda_stream, rs, d_wav, d_rs[:K + 1], d_off if aug is None else d_aug[:K + 1],
+                                         d_rs[K + 1:], d_taps, True, self.device)
+            if aug is not None:
                 d_wav, _ = _tempo_gain_launch(lib, self.stream.cuda_stream, aug, d_wav, d_aug[:K + 1], d_off, d_aug[K + 1:], d_tempo, d_gain,
                                               True, self.device)
             if noise is None:
@@ -793,6 +993,10 @@ class SpectrogramFrontEnd:
         inputs.record_stream(self.consumer)
         return inputs, torch.from_numpy(frames)
 
+
+    def resample(self, waves, rates, quantize=True):
+        """`resample` to this front-end's sample rate on its device: list of K converted float32 numpy arrays"""
+        return resample(waves, rates, self.sample_rate, quantize, self.device)
 
     def tempo_gain(self, waves, tempo, gain_db, quantize=True):
         """`tempo_gain` at this front-end's sample rate and device: (list of K stretched float32 numpy arrays, seg_off)"""

@@ -33,6 +33,17 @@ mtl_spect_batch_noise and mtl_wave_mix_coef alone.
 plus the HIP-event times of mtl_tempo_search, mtl_tempo_render and of mtl_spect_batch on the stretched buffer alone.
 
     python tools/bench_frontend.py --augment --augment-out profiles/frontend_augment.json
+
+--resample [--resample-out PATH] runs the rate-conversion leg instead, same protocol, three paths that alternate over
+K = 16 ten-second utterances at 8 kHz (80 000 samples each) for a 16 kHz front-end:
+
+  (a) device:   `batch(waves, rates=[8000] * K)`
+  (b) host:     `scipy.signal.resample_poly(y, 2, 1)` per utterance on the calling thread, then `batch(converted)`: what a user does today
+  (c) at rate:  `batch` of audio that is at 16 kHz already, of the same output length (the floor: no conversion at all)
+
+plus the HIP-event time of mtl_resample alone and the bytes it reads and writes over that time, against the HBM rate.
+
+    python tools/bench_frontend.py --resample --resample-out profiles/frontend_resample.json
 """
 import argparse
 import json
@@ -65,6 +76,8 @@ def main():
     ap.add_argument('--noise-out', default=None)
     ap.add_argument('--augment', action='store_true')
     ap.add_argument('--augment-out', default=None)
+    ap.add_argument('--resample', action='store_true')
+    ap.add_argument('--resample-out', default=None)
     a = ap.parse_args()
     if a.reps < 20 or a.warmup < 3:
         ap.error('at least 20 timed calls after at least 3 warm-ups')
@@ -80,6 +93,8 @@ def main():
         return noise_leg(a, mtl_amd, _lib, fe, waves)
     if a.augment or a.augment_out:
         return augment_leg(a, mtl_amd, _lib, fe, waves, labels)
+    if a.resample or a.resample_out:
+        return resample_leg(a, mtl_amd, _lib, fe, waves)
 
     def per_utterance():
         specs = [fe(y).cpu() for y in waves]
@@ -380,6 +395,112 @@ def augment_leg(a, mtl_amd, _lib, fe, waves, labels):
     print(json.dumps(res))
     if a.augment_out:
         with open(a.augment_out, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write('\n')
+
+
+HBM_TBPS = 8.0          # MI355X: 8 TB/s of HBM3E bandwidth (the vendor's figure)
+
+
+def resample_leg(a, mtl_amd, _lib, fe, waves16):
+    from scipy.signal import resample_poly
+    K, dev, rate = len(waves16), fe.device, 8000
+    # ten seconds at 8 kHz, as a 16-bit file holds them; the 16 kHz audio of path (c) has the length that the conversion gives
+    waves = [(np.rint(y[::2].astype(np.float64) * 32768.0) / 32768.0).astype(np.float32) for y in waves16]
+    rates = [rate] * K
+    out_lengths = mtl_amd.resample_plan([len(y) for y in waves], rates, fe.sample_rate)[0]
+    at_rate = [y[:n] for y, n in zip(waves16, out_lengths)]
+    assert [len(y) for y in at_rate] == out_lengths.tolist()
+
+    def device():
+        return fe.batch(waves, rates=rates)[0]
+
+    def host():
+        return fe.batch([resample_poly(y, 2, 1).astype(np.float32) for y in waves])[0]
+
+    def same_length():
+        return fe.batch(at_rate)[0]
+
+    # the converted batch must be the batch of the unfused form's waveforms, and close to the host's, before its time means anything
+    converted = fe.resample(waves, rates)
+    xa, xb, xc = device(), host(), fe.batch(converted)[0]
+    torch.cuda.synchronize()
+    assert [len(c) for c in converted] == out_lengths.tolist() and torch.equal(xa, xc) and xa.shape == xb.shape
+    vs_host = max(float((xa[k].double() - xb[k].double()).norm() / xb[k].double().norm()) for k in range(K))
+
+    m = torch.randn(4096, 4096, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        m @ m
+    e0.record()
+    for _ in range(20):
+        m @ m
+    e1.record()
+    torch.cuda.synchronize()
+    chain = max(int(round(a.queued_ms / (e0.elapsed_time(e1) / 20))), 1)
+
+    def timed(fn, busy):
+        torch.cuda.synchronize()
+        if busy:
+            for _ in range(chain):
+                m @ m
+        t0 = time.perf_counter()
+        x = fn()
+        dt = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        del x
+        return dt
+
+    paths = (('device', device), ('host', host), ('at_rate', same_length))
+    times = {(name, busy): [] for name, _ in paths for busy in (False, True)}
+    for rep in range(a.warmup + a.reps):
+        for busy in (False, True):
+            for name, fn in paths:
+                dt = timed(fn, busy)
+                if rep >= a.warmup:
+                    times[(name, busy)].append(dt)
+    host_convert_ms = []
+    for rep in range(a.warmup + a.reps):
+        t0 = time.perf_counter()
+        [resample_poly(y, 2, 1).astype(np.float32) for y in waves]
+        if rep >= a.warmup:
+            host_convert_ms.append(1e3 * (time.perf_counter() - t0))
+
+    # device time of the launch alone (operands on the device)
+    lib = _lib.lib()
+    tab = mtl_amd.resample_tables(waves, rates, fe.sample_rate)
+    d = {k: torch.from_numpy(tab[k]).to(dev) for k in ('flat', 'offsets', 'out_offsets', 'plan', 'taps')}
+    d_out = torch.empty(int(tab['out_offsets'][-1]), device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    launch_us = []
+    for rep in range(a.warmup + a.reps):
+        torch.cuda.synchronize()
+        e0.record()
+        _lib.check(lib.mtl_resample(st, d['flat'].data_ptr(), d['offsets'].data_ptr(), d['out_offsets'].data_ptr(), d['plan'].data_ptr(),
+                                    d['taps'].data_ptr(), tab['taps'].shape[0], K, 1, d_out.data_ptr()), 'mtl_resample')
+        e1.record()
+        torch.cuda.synchronize()
+        if rep >= a.warmup:
+            launch_us.append(1e3 * e0.elapsed_time(e1))
+    assert np.array_equal(d_out.cpu().numpy(), np.concatenate(converted))
+    moved = 4 * tab['flat'].shape[0] + 4 * d_out.numel() + 8 * tab['taps'].shape[0] + 8 * (2 * (K + 1) + 4 * K)
+    terms = int(tab['out_offsets'][-1]) * (tab['taps'].shape[0] // int(tab['plan'][0, 0]) + 1)
+    tbps = moved / (statistics.median(launch_us) * 1e-6) / 1e12
+
+    key = lambda n, b: '%s_%s' % (n, 'busy' if b else 'idle')
+    res = dict(device=torch.cuda.get_device_name(0), utterances=K, samples_per_utterance=len(waves[0]), rate_in=rate, rate_out=fe.sample_rate,
+               converted_samples_per_utterance=int(out_lengths[0]), taps=int(tab['taps'].shape[0]), reps=a.reps, warmup=a.warmup,
+               queued_ms=a.queued_ms, queued_products=chain, worst_rel_device_vs_host_features=vs_host,
+               utt_per_s={key(n, b): K / statistics.median(v) for (n, b), v in times.items()},
+               call_ms_median={key(n, b): 1e3 * statistics.median(v) for (n, b), v in times.items()},
+               call_ms_min_max={key(n, b): [1e3 * min(v), 1e3 * max(v)] for (n, b), v in times.items()},
+               host_resample_poly_ms_median=statistics.median(host_convert_ms),
+               launch_us_median=statistics.median(launch_us), launch_us_min=min(launch_us), launch_bytes=moved,
+               launch_tb_per_s=tbps, hbm_tb_per_s=HBM_TBPS, launch_share_of_hbm_rate=tbps / HBM_TBPS,
+               launch_fp64_gflops=2.0 * terms / (statistics.median(launch_us) * 1e-6) / 1e9)
+    print(json.dumps(res))
+    if a.resample_out:
+        with open(a.resample_out, 'w') as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write('\n')
 
