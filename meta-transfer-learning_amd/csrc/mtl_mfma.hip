@@ -1628,6 +1628,7 @@ int launch_conv_x3h(ConvX3P p, int Te, int Fe, hipStream_t s) {
     p.ntf = (Fe + 15) / 16;
     p.ntt = (Te + 8 * G - 1) / (8 * G);
     p.tiles = p.ntf * p.ntt * p.g.B * p.ntile;
+    if (p.tiles <= 0) return MTL_OK;                           // empty extent (a pooled forward with T < 2 or F < 2): no output, no launch
     const int grid = p.tiles < ncu * per_cu ? p.tiles : ncu * per_cu;
     hipLaunchKernelGGL((conv3x3_x3h_kernel<BN, G, UNPOOL, EPI, NP, WN>), dim3(grid), dim3(THREADS), SMEM, s, p);
     MTL_CHECK_LAUNCH();
@@ -2812,7 +2813,7 @@ static int conv_dgrad_pieces(hipStream_t s, const float* dy, const float* amax_d
 #ifndef MTL_DGRAD_EDGE
 #define MTL_DGRAD_EDGE 1     // (0: probe builds for A/B runs -- the matrix kernel spends a tile column on the last frequency bin)
 #endif
-    const bool edge = MTL_DGRAD_EDGE && (F & 1) && F >= 3 && Cin == EDGE_C && Cout == EDGE_C && B * tk.tasks <= 65535;
+    const bool edge = MTL_DGRAD_EDGE && (F & 1) && F >= 3 && T >= 1 && Cin == EDGE_C && Cout == EDGE_C && B * tk.tasks <= 65535;
     const int rc = dispatch_conv_x3<true, EPI_DGRAD, NP>(p, T, edge ? F - 1 : F, s);
     if (rc != MTL_OK || !edge) return rc;
     static int attr = set_smem(conv_dgrad_edge_kernel<NP>, EDGE_SMEM);
@@ -3044,6 +3045,7 @@ static int wgrad_pieces(hipStream_t s, const float* x, const float* amax_x, cons
     p.ntf = (p.Fy + 15) / 16;
     p.ntt = (p.Ty + 7) / 8;
     p.tiles = p.ntf * p.ntt * B;
+    if (p.tiles <= 0) return MTL_OK;                            // empty extent (pooled, T < 2 or F < 2): dw / db keep their values, no launch
     p.dbg = 0;
     p.amax_x = amax_x;
     p.amax_dy = amax_dy;
