@@ -467,6 +467,30 @@ int mtl_tempo_render(void* stream, const float* wav, const long* offsets, const 
  *   launch.  One launch, no workspace, no atomics: bitwise repeatable.  out has sum of N_k floats. */
 int mtl_resample(void* stream, const float* wav, const long* offsets, const long* out_offsets, const long* plan, const double* taps,
                  long n_taps, int K, int quantize, float* out);
+/* Log-mel filterbank front-end for a sampled batch of K utterances in two launches (csrc/mtl_fbank.hip; LogFBankDataset.parse_audio,
+ * utils/data_loader.py:145-155 per utterance: logfbank(sig, rate, nfilt = 80) of python_speech_features with its defaults; that library
+ * is not reproduced from its source: the behaviour is DEFINED in DESIGN.md section 15, parity unpinned).  wav / offsets as in
+ * mtl_spect_batch (utterance k: L_k >= 1 samples of pcm16 / 32768).  Per utterance: s = 32768 x, p[0] = s[0], p[i] = s[i] - 0.97 s[i-1];
+ * T_k = 1 for L_k <= fl, else 1 + ceil((L_k - fl) / fs); frame t = p[t fs .. t fs + fl), zeros past L_k, rectangular window;
+ * P[t][f] = |DFT_nfft(frame t)[f]|^2 / nfft for f = 0 .. nfft / 2; E[j][t] = sum_f w[j][f] P[t][f]; v = ln E, or ln(2^-52) where E == 0.
+ *   basis: fl x ldb floats, row n = cos(2 pi f n / nfft) for f = 0 .. nfft / 2, then -sin(...) for the same bins (ldb >= nfft + 2)
+ *   band: nfilt x 3 ints (first bin, count, offset into band_w): w[j][first + i] = band_w[offset + i], i < count, every other weight 0;
+ *     band_w has n_w floats.  A band whose range leaves [0, nfft / 2] or [0, n_w) is read as empty.
+ *   out: (K, nfilt, Tmax) fp32, out[k][j][t] = v for t < min(T_k, Tmax) and 0 behind; normalize != 0: (v - mean_k) / std_k with the
+ *     statistics in fp64 over ALL nfilt T_k values of utterance k (unbiased std), also when Tmax < T_k.  The std is used as it comes, as in
+ *     mtl_spect_batch: an utterance without variance is divided by zero.
+ * The frames are formed inside the kernel from an LDS-staged span (no frame matrix and no power spectrum in memory), the DFT runs on
+ * v_mfma_f32_16x16x4_f32, the statistics are fp64 partials combined in a fixed order: bitwise repeatable, no atomics, and utterance k's
+ * rows depend on utterance k alone.  The grid does not depend on the lengths.  A workgroup takes mtl_fbank_tile_frames() consecutive
+ * frames at a time and mtl_fbank_slots() workgroups share an utterance.  workspace: mtl_fbank_batch_workspace(K) bytes, 8-byte aligned.
+ * K < 1, fl < 1, fl > nfft, fs < 1, nfilt < 1, Tmax < 1, nfft odd or outside [2, 512], ldb < nfft + 2, n_w < 1, a null pointer or a short
+ * workspace return -22 before any launch. */
+long mtl_fbank_batch_workspace(int K);
+int mtl_fbank_tile_frames(void);
+int mtl_fbank_slots(void);
+int mtl_fbank_batch(void* stream, const float* wav, const long* offsets, int K, int fl, int fs, int nfft, const float* basis, int ldb,
+                    int nfilt, const int* band, const float* band_w, int n_w, float* out, int Tmax, int normalize, void* workspace,
+                    long workspace_bytes);
 
 /* ---- accent discriminator on the encoder output (joint_train.py --multitask / --adversarial) ------------------------------
  * modules/discriminator.py, trainer/asr/joint_trainer.py:29-37, utils/metrics.py:164-199 (csrc/mtl_disc.hip):

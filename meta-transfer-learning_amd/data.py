@@ -318,6 +318,43 @@ class ManifestTaskDataset:
         return self._feature(row[0], None if draws is None else draws[0])[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
 
 
+def _wav_dataset_options(ds, audio_conf, feature_fn, augment, device_batches, resample, input_type, char_lines):
+    """the rejections that SpectrogramDataset and LogFBankDataset share, in front of their base constructor, and the noise injector:
+    sets ds.noiseInjector and returns the `noise=` of ManifestTaskDataset, (injector, noise_prob) or None"""
+    if resample and feature_fn is not None:
+        raise NotImplementedError('sample rates are converted on the device: resample=True cannot be combined with a feature_fn (which '
+                                  'gets paths)')
+    if device_batches and feature_fn is not None:
+        raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
+    if augment and feature_fn is not None:
+        raise NotImplementedError('augment=True (tempo / gain perturbation, utils/data_loader.py:28-38) runs on the device: it cannot '
+                                  'be combined with a feature_fn (which gets paths)')
+    if augment and not device_batches:
+        raise NotImplementedError('augment=True (tempo / gain perturbation, utils/data_loader.py:28-38) exists in the batched device '
+                                  'path only: pass device_batches=True')
+    noise = None
+    if audio_conf.get('noise_dir') is not None:
+        if feature_fn is not None:
+            raise NotImplementedError("noise injection (audio_conf['noise_dir']) mixes samples on the device: it cannot be combined "
+                                      "with a feature_fn (which gets paths)")
+        ds.noiseInjector = NoiseInjection(audio_conf['noise_dir'], audio_conf['sample_rate'], audio_conf.get('noise_levels', (0, 0.5)))
+        noise = (ds.noiseInjector, float(audio_conf.get('noise_prob')))
+    else:
+        ds.noiseInjector = None
+    if input_type != 'char':
+        raise NotImplementedError("only input_type='char' (utils/data_loader.py:%s)" % char_lines)
+    return noise
+
+
+def _wav_dataset_wiring(ds, noise, augment, resample, device_batches, front_end, manifest_filepath_list, input_type):
+    """... and what both set behind it (after the base constructor: the default feature_fn is no user's)"""
+    ds._noise = noise
+    ds._augment = TempoGainAugment() if augment else None
+    ds._resample, ds._rate = bool(resample), ds.sample_rate
+    ds.device_batches, ds._fe_factory = device_batches, front_end       # (sample() of a part: one front_end().batch call)
+    ds.manifest_filepath_list, ds.input_type = manifest_filepath_list, input_type
+
+
 class SpectrogramDataset(ManifestTaskDataset):
     """utils/data_loader.py:171-236 with the reference's OWN constructor, so that its entry script builds the datasets unchanged
     (meta_transfer_train.py:159-175):
@@ -344,28 +381,7 @@ class SpectrogramDataset(ManifestTaskDataset):
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
                  is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False):
-        if resample and feature_fn is not None:
-            raise NotImplementedError('sample rates are converted on the device: resample=True cannot be combined with a feature_fn (which '
-                                      'gets paths)')
-        if device_batches and feature_fn is not None:
-            raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
-        if augment and feature_fn is not None:
-            raise NotImplementedError('augment=True (tempo / gain perturbation, utils/data_loader.py:28-38) runs on the device: it cannot '
-                                      'be combined with a feature_fn (which gets paths)')
-        if augment and not device_batches:
-            raise NotImplementedError('augment=True (tempo / gain perturbation, utils/data_loader.py:28-38) exists in the batched device '
-                                      'path only: pass device_batches=True')
-        noise = None
-        if audio_conf.get('noise_dir') is not None:
-            if feature_fn is not None:
-                raise NotImplementedError("noise injection (audio_conf['noise_dir']) mixes samples on the device: it cannot be combined "
-                                          "with a feature_fn (which gets paths)")
-            self.noiseInjector = NoiseInjection(audio_conf['noise_dir'], audio_conf['sample_rate'], audio_conf.get('noise_levels', (0, 0.5)))
-            noise = (self.noiseInjector, float(audio_conf.get('noise_prob')))
-        else:
-            self.noiseInjector = None
-        if input_type != 'char':
-            raise NotImplementedError("only input_type='char' (utils/data_loader.py:342-361)")
+        noise = _wav_dataset_options(self, audio_conf, feature_fn, augment, device_batches, resample, input_type, '342-361')
         self.window_stride, self.window_size = audio_conf['window_stride'], audio_conf['window_size']
         self.sample_rate, self.window = audio_conf['sample_rate'], audio_conf.get('window', 'hamming')
         self.normalize, self.augment, self.noise_prob = normalize, augment, audio_conf.get('noise_prob')
@@ -381,11 +397,7 @@ class SpectrogramDataset(ManifestTaskDataset):
             def feature_fn(path):
                 return front_end()(load_wav_pcm16(path)).cpu()
         super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
-        self._noise = noise                                          # (after the base constructor: the default feature_fn is no user's)
-        self._augment = TempoGainAugment() if augment else None
-        self._resample, self._rate = bool(resample), self.sample_rate
-        self.device_batches, self._fe_factory = device_batches, front_end       # (sample() of a part: one front_end().batch call)
-        self.manifest_filepath_list, self.input_type = manifest_filepath_list, input_type
+        _wav_dataset_wiring(self, noise, augment, resample, device_batches, front_end, manifest_filepath_list, input_type)
         # (the reference leaves part_len at the LAST manifest's partition size, or max_size without partitions: :211-222)
         self.part_len = (max(int(len(self.ids_list[-1]) * partitions[len(self.ids_list) - 1]), 1) if partitions is not None
                          else self.max_size)
@@ -780,6 +792,8 @@ class SpectrogramFrontEnd:
     center + reflect padding = librosa.stft defaults of the reference era) -> |.| -> log1p -> (x-mean)/std, all on the MI355X:
     the STFT is one fp32-MFMA GEMM (frames = overlapping rows of the padded waveform, lda = hop) against a windowed DFT basis."""
 
+    _NAME = 'spectrogram'                                      # (in the messages of `batch`, which LogFBankFrontEnd shares)
+
     def __init__(self, sample_rate=16000, window_size=0.02, window_stride=0.01, window='hamming', normalize=True, device='cuda',
                  consumer=None):
         """consumer: the stream on which the batches of `batch()` are read (default: the device's current stream at construction --
@@ -802,6 +816,9 @@ class SpectrogramFrontEnd:
         basis[:, self.F:2 * self.F] = (-win[:, None] * np.sin(ang)).astype(np.float32)
         self.basis = torch.from_numpy(basis).to(self.device)
         self.partials = torch.empty(512, dtype=torch.float64, device=self.device)
+        self._init_batch_state(consumer)
+
+    def _init_batch_state(self, consumer):
         self.consumer = consumer if consumer is not None or self.device.type != 'cuda' else torch.cuda.current_stream(self.device)
         self.stream = None                                     # batch()'s own stream, made at its first call
         self._pin_wav = self._pin_off = None                   # pinned staging of batch(), grown on demand
@@ -869,11 +886,11 @@ class SpectrogramFrontEnd:
         issues exactly the calls described above."""
         from . import _lib
         if self.device.type != 'cuda':
-            raise RuntimeError('the spectrogram front-end runs on the MI355X only (no CPU fallback)')
+            raise RuntimeError('the %s front-end runs on the MI355X only (no CPU fallback)' % self._NAME)
         lib = _lib.lib()
         aug = rs = None
         if augment is None and rates is None:
-            flat, offsets, frames, tmax = pack_waveforms(waves, self.hop, self.n_fft, max_frames)
+            flat, offsets, frames, tmax = self._pack(waves, max_frames)
         else:
             # the samples that are uploaded are the original ones; everything downstream sees the converted / stretched lengths
             if rates is not None:
@@ -885,21 +902,14 @@ class SpectrogramFrontEnd:
             elif augment is not None:
                 aug = _tempo_gain_plan(np.diff(rs['out_offsets']), augment[0], augment[1], self.sample_rate)
                 offsets = aug['out_offsets']
-            short = np.flatnonzero(np.diff(offsets) < self.n_fft // 2 + 1)
-            if short.size:
-                raise ValueError('batch: utterance %d has %d samples after the %s, fewer than n_fft // 2 + 1 = %d (one reflection '
-                                 'must suffice)' % (short[0], np.diff(offsets)[short[0]], 'rate conversion' if aug is None else 'tempo change',
-                                                    self.n_fft // 2 + 1))
-            frames = 1 + np.diff(offsets) // self.hop
+            self._check_lengths(np.diff(offsets), 'rate conversion' if aug is None else 'tempo change')
+            frames = self._frame_counts(np.diff(offsets))
             if max_frames is not None:
                 frames = np.minimum(frames, max_frames)
             frames = frames.astype(np.int32)
             tmax = int(frames.max())
         K = len(frames)
-        total_frames = int((1 + np.diff(offsets) // self.hop).sum())
-        ws_bytes = lib.mtl_spect_batch_workspace(total_frames, K, self.F)
-        if ws_bytes < 0:
-            raise RuntimeError('mtl_spect_batch_workspace failed with code %d' % ws_bytes)
+        ws_bytes = self._workspace_bytes(lib, np.diff(offsets), K)
         if self.stream is None:
             self.stream = torch.cuda.Stream(self.device)
         if self._pin_wav is None or self._pin_wav.numel() < flat.shape[0]:
@@ -970,9 +980,7 @@ class SpectrogramFrontEnd:
                 d_wav, _ = _tempo_gain_launch(lib, self.stream.cuda_stream, aug, d_wav, d_aug[:K + 1], d_off, d_aug[K + 1:], d_tempo, d_gain,
                                               True, self.device)
             if noise is None:
-                _lib.check(lib.mtl_spect_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
-                                               self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax, 1 if self.normalize else 0,
-                                               ws.data_ptr(), ws_bytes), 'mtl_spect_batch')
+                self._features_launch(lib, d_wav, d_off, K, inputs, tmax, ws, ws_bytes, None)
             else:
                 d_noff = torch.empty(K, dtype=torch.int64, device=self.device)
                 d_lvl = torch.empty(K, dtype=torch.float32, device=self.device)
@@ -983,16 +991,46 @@ class SpectrogramFrontEnd:
                 _lib.check(lib.mtl_wave_mix_coef(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, bank.data_ptr(),
                                                  injector.bank_len, d_noff.data_ptr(), d_lvl.data_ptr(), coef.data_ptr(), cws.data_ptr(),
                                                  cws_bytes), 'mtl_wave_mix_coef')
-                _lib.check(lib.mtl_spect_batch_noise(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
-                                                     self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax,
-                                                     1 if self.normalize else 0, ws.data_ptr(), ws_bytes, bank.data_ptr(), injector.bank_len,
-                                                     d_noff.data_ptr(), coef.data_ptr()), 'mtl_spect_batch_noise')
+                self._features_launch(lib, d_wav, d_off, K, inputs, tmax, ws, ws_bytes, (bank, injector.bank_len, d_noff, coef))
             done = torch.cuda.Event()
             done.record(self.stream)
         done.synchronize()                                     # host wait on this stream's event only
         inputs.record_stream(self.consumer)
         return inputs, torch.from_numpy(frames)
 
+    # what `batch` asks of the feature type (LogFBankFrontEnd overrides these five and nothing else of `batch`)
+    def _pack(self, waves, max_frames):
+        return pack_waveforms(waves, self.hop, self.n_fft, max_frames)
+
+    def _check_lengths(self, lengths, stage):
+        short = np.flatnonzero(lengths < self.n_fft // 2 + 1)
+        if short.size:
+            raise ValueError('batch: utterance %d has %d samples after the %s, fewer than n_fft // 2 + 1 = %d (one reflection '
+                             'must suffice)' % (short[0], lengths[short[0]], stage, self.n_fft // 2 + 1))
+
+    def _frame_counts(self, lengths):
+        return 1 + lengths // self.hop
+
+    def _workspace_bytes(self, lib, lengths, K):
+        ws_bytes = lib.mtl_spect_batch_workspace(int(self._frame_counts(lengths).sum()), K, self.F)
+        if ws_bytes < 0:
+            raise RuntimeError('mtl_spect_batch_workspace failed with code %d' % ws_bytes)
+        return ws_bytes
+
+    def _features_launch(self, lib, d_wav, d_off, K, inputs, tmax, ws, ws_bytes, mix):
+        """the last call of `batch` on its stream: packed waveforms -> inputs.  mix = (bank, bank_len, d_noff, coef) behind
+        mtl_wave_mix_coef, or None for clean utterances"""
+        from . import _lib
+        if mix is None:
+            _lib.check(lib.mtl_spect_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
+                                           self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax, 1 if self.normalize else 0,
+                                           ws.data_ptr(), ws_bytes), 'mtl_spect_batch')
+        else:
+            bank, bank_len, d_noff, coef = mix
+            _lib.check(lib.mtl_spect_batch_noise(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.n_fft, self.hop,
+                                                 self.basis.data_ptr(), self.ldb, self.F, inputs.data_ptr(), tmax,
+                                                 1 if self.normalize else 0, ws.data_ptr(), ws_bytes, bank.data_ptr(), bank_len,
+                                                 d_noff.data_ptr(), coef.data_ptr()), 'mtl_spect_batch_noise')
 
     def resample(self, waves, rates, quantize=True):
         """`resample` to this front-end's sample rate on its device: list of K converted float32 numpy arrays"""
@@ -1001,6 +1039,209 @@ class SpectrogramFrontEnd:
     def tempo_gain(self, waves, tempo, gain_db, quantize=True):
         """`tempo_gain` at this front-end's sample rate and device: (list of K stretched float32 numpy arrays, seg_off)"""
         return tempo_gain(waves, tempo, gain_db, self.sample_rate, quantize, self.device)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Log-mel filterbank front-end on the device (LogFBankDataset.parse_audio, utils/data_loader.py:145-155); DESIGN.md section 15
+# ------------------------------------------------------------------------------------------------------------------
+FBANK_EPS = 2.220446049250313e-16          # what an energy of exactly zero becomes before the logarithm
+
+
+def fbank_geometry(rate):
+    """(fl, fs, nfft) of the 25 ms / 10 ms framing at `rate`: fl = floor(0.025 R + 0.5), fs = floor(0.01 R + 0.5), nfft = 512 (400 / 160 at
+    16 kHz, 200 / 80 at 8 kHz).  A rate whose frame is longer than the transform (R > 20480) raises ValueError: the library would cut the
+    frames, and that is not reproduced."""
+    import math
+    fl, fs, nfft = int(math.floor(0.025 * rate + 0.5)), int(math.floor(0.01 * rate + 0.5)), 512
+    if fl < 1 or fs < 1:
+        raise ValueError('fbank_geometry: a sample rate of %r Hz has no 25 ms frame' % (rate,))
+    if fl > nfft:
+        raise ValueError('fbank_geometry: a 25 ms frame at %r Hz has %d samples, more than nfft = %d' % (rate, fl, nfft))
+    return fl, fs, nfft
+
+
+def fbank_frames(lengths, rate):
+    """frames of utterances of `lengths` samples (each >= 1) at `rate`: 1 for L <= fl, else 1 + ceil((L - fl) / fs); int64 array"""
+    fl, fs, _ = fbank_geometry(rate)
+    lengths = np.array(lengths, dtype=np.int64).reshape(-1)
+    if (lengths < 1).any():
+        raise ValueError('fbank_frames: an utterance without samples')
+    return np.where(lengths <= fl, 1, 1 + (lengths - fl + fs - 1) // fs).astype(np.int64)
+
+
+def mel_filterbank(nfilt=80, nfft=512, rate=16000):
+    """the dense (nfilt, nfft // 2 + 1) fp64 table of triangular mel bands: mel points linspace(mel(0), mel(R / 2), nfilt + 2) with
+    mel(h) = 2595 log10(1 + h / 700), bins b[j] = floor((nfft + 1) hz(m_j) / R), band j rising over [b[j], b[j+1]) and falling over
+    [b[j+1], b[j+2]).  At 16 kHz the bins begin 0, 0, 1, 2, 2, 3, so band 2 has no weight at all: kept, not repaired."""
+    high = rate / 2.0
+    m = np.linspace(2595.0 * np.log10(1.0 + 0.0 / 700.0), 2595.0 * np.log10(1.0 + high / 700.0), nfilt + 2)
+    b = np.floor((nfft + 1) * (700.0 * (10.0 ** (m / 2595.0) - 1.0)) / rate)
+    fb = np.zeros((nfilt, nfft // 2 + 1), dtype=np.float64)
+    for j in range(nfilt):
+        for i in range(int(b[j]), int(b[j + 1])):
+            fb[j, i] = (i - b[j]) / (b[j + 1] - b[j])
+        for i in range(int(b[j + 1]), int(b[j + 2])):
+            fb[j, i] = (b[j + 2] - i) / (b[j + 2] - b[j + 1])
+    return fb
+
+
+def mel_filterbank_sparse(fb):
+    """dense table -> (band int32 (nfilt, 3): first bin, count, offset of the band's weights; weights float32, never empty): per band
+    the range from its first to its last non-zero weight, rounded once to fp32.  A band without weight has count 0."""
+    band, w = np.zeros((fb.shape[0], 3), dtype=np.int32), []
+    for j in range(fb.shape[0]):
+        nz = np.flatnonzero(fb[j])
+        if nz.size:
+            band[j] = nz[0], nz[-1] - nz[0] + 1, len(w)
+            w.extend(fb[j, nz[0]:nz[-1] + 1])
+    return band, np.array(w if w else [0.0], dtype=np.float32)
+
+
+class LogFBankFrontEnd(SpectrogramFrontEnd):
+    """wav -> `nfilt` log mel filterbank energies per 25 ms frame every 10 ms (logfbank(sig, rate, nfilt=80) of python_speech_features
+    with its defaults, restated in DESIGN.md section 15: scale to int16 values, pre-emphasis 0.97, rectangular 25 ms frames without
+    centring, |DFT_512|^2 / 512, triangular mel bands, ln, energy 0 -> ln(2^-52)) -> (x - mean) / std over the utterance, all on the
+    MI355X in the two launches of mtl_fbank_batch.  `batch` is SpectrogramFrontEnd.batch -- streams, pinned staging, record_stream, and the
+    rate / tempo / noise stages in front of the last call -- with this feature type's frame count (`fbank_frames`), a minimum length of
+    one sample, and mtl_fbank_batch as the last call (behind the unfused mtl_wave_mix when noise is given).  Only that method and its
+    five hooks are shared: the base constructor is not called (no window, no STFT basis, no `partials`)."""
+
+    _NAME = 'log-mel filterbank'
+
+    def __init__(self, sample_rate=16000, nfilt=80, normalize=True, device='cuda', consumer=None):
+        self.sample_rate = sample_rate
+        self.fl, self.fs, self.nfft = fbank_geometry(sample_rate)
+        self.nfilt = self.F = int(nfilt)
+        if self.nfilt < 1:
+            raise ValueError('LogFBankFrontEnd: nfilt must be positive, got %r' % (nfilt,))
+        self.normalize = normalize
+        self.device = torch.device(device)
+        nbins = self.nfft // 2 + 1
+        ang = 2.0 * np.pi * np.arange(self.fl, dtype=np.float64)[:, None] * np.arange(nbins, dtype=np.float64)[None, :] / self.nfft
+        self.ldb = (2 * nbins + 3) // 4 * 4
+        basis = np.zeros((self.fl, self.ldb), dtype=np.float32)          # fp64, rounded once; only fl rows: the zero padding is free
+        basis[:, :nbins] = np.cos(ang).astype(np.float32)
+        basis[:, nbins:2 * nbins] = (-np.sin(ang)).astype(np.float32)
+        self.filterbank = mel_filterbank(self.nfilt, self.nfft, sample_rate)
+        band, w = mel_filterbank_sparse(self.filterbank)
+        self.basis = torch.from_numpy(basis).to(self.device)
+        self.band, self.band_w = torch.from_numpy(band).to(self.device), torch.from_numpy(w).to(self.device)
+        self._init_batch_state(consumer)
+
+    def __call__(self, y):
+        """y: 1-D float waveform (numpy or tensor, >= 1 sample) -> (nfilt, T) fp32 tensor on the device, T = fbank_frames([len(y)])"""
+        return self.batch([y])[0][0, 0]
+
+    def batch(self, waves, max_frames=None, noise=None, augment=None, rates=None):
+        """K waveforms -> (inputs (K, 1, nfilt, Tmax) fp32 on the device, input_sizes (K) int32 on the host): what `collate` builds from
+        K `__call__` results cut to max_frames, in one device pass -- one pinned staging copy of the concatenated samples and of the
+        offsets and the two launches of mtl_fbank_batch (staging with scaling and pre-emphasis, the 512-point DFT, power, bands, ln,
+        per-utterance statistics over the WHOLE utterance, normalisation, zero padding).  input_sizes are `fbank_frames` of the
+        lengths, cut to max_frames; an utterance needs one sample.
+
+        Streams, pinned staging and `record_stream` are those of SpectrogramFrontEnd.batch (it is that method), and so are the
+        meanings of the three optional stages, each of which leaves a packed waveform in front of the last call:
+        rates= converts utterance k from rates[k] to this front-end's rate (mtl_resample), augment=(tempo, gain_db) stretches and
+        amplifies it (mtl_tempo_search, mtl_tempo_render), noise=(injector, noise_off, level) mixes it with the injector's bank
+        (mtl_wave_mix_coef, then the UNFUSED mtl_wave_mix into a second packed buffer: the mix is not folded into this kernel's
+        staging).  The result is bitwise `batch` of the waveforms that `resample`, `tempo_gain` and mtl_wave_mix give; frame counts and
+        the one-sample minimum refer to the converted / stretched lengths.  With none of them exactly the calls above are issued."""
+        return super().batch(waves, max_frames=max_frames, noise=noise, augment=augment, rates=rates)
+
+    def _pack(self, waves, max_frames):
+        if len(waves) == 0:
+            raise ValueError('batch: an empty list of waveforms')
+        arrs = []
+        for i, w in enumerate(waves):
+            a = np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float32)
+            if a.ndim != 1:
+                raise ValueError('batch: waveform %d is not one-dimensional (shape %s)' % (i, a.shape))
+            arrs.append(a)
+        lengths = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+        self._check_lengths(lengths, 'load')
+        offsets = np.zeros(len(arrs) + 1, dtype=np.int64)
+        np.cumsum(lengths, out=offsets[1:])
+        frames = self._frame_counts(lengths)
+        if max_frames is not None:
+            frames = np.minimum(frames, max_frames)
+        frames = frames.astype(np.int32)
+        return np.concatenate(arrs), offsets, frames, int(frames.max())
+
+    def _check_lengths(self, lengths, stage):
+        short = np.flatnonzero(lengths < 1)
+        if short.size:
+            raise ValueError('batch: utterance %d has no samples after the %s' % (short[0], stage))
+
+    def _frame_counts(self, lengths):
+        return fbank_frames(lengths, self.sample_rate)
+
+    def _workspace_bytes(self, lib, lengths, K):
+        ws_bytes = lib.mtl_fbank_batch_workspace(K)
+        if ws_bytes < 0:
+            raise RuntimeError('mtl_fbank_batch_workspace failed with code %d' % ws_bytes)
+        return ws_bytes
+
+    def _features_launch(self, lib, d_wav, d_off, K, inputs, tmax, ws, ws_bytes, mix):
+        from . import _lib
+        if mix is not None:                                    # the unfused mix: a packed buffer of the mixed waveforms, same offsets
+            bank, bank_len, d_noff, coef = mix
+            mixed = torch.empty_like(d_wav)
+            _lib.check(lib.mtl_wave_mix(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, bank.data_ptr(), bank_len,
+                                        d_noff.data_ptr(), coef.data_ptr(), mixed.data_ptr()), 'mtl_wave_mix')
+            d_wav = mixed
+        _lib.check(lib.mtl_fbank_batch(self.stream.cuda_stream, d_wav.data_ptr(), d_off.data_ptr(), K, self.fl, self.fs, self.nfft,
+                                       self.basis.data_ptr(), self.ldb, self.nfilt, self.band.data_ptr(), self.band_w.data_ptr(),
+                                       self.band_w.numel(), inputs.data_ptr(), tmax, 1 if self.normalize else 0, ws.data_ptr(), ws_bytes),
+                   'mtl_fbank_batch')
+
+
+class LogFBankDataset(ManifestTaskDataset):
+    """utils/data_loader.py:101-168 with the reference's OWN constructor (test.py:199-200):
+
+        LogFBankDataset(vocab, args, audio_conf, manifest_filepath_list=..., normalize=True, augment=False, input_type='char')
+
+    80 log mel filterbank energies per frame from the device front-end (LogFBankFrontEnd at audio_conf['sample_rate']) unless a
+    `feature_fn` is given.  Same attributes as the reference object (max_size = longest manifest x manifests, ids_list, input_type,
+    manifest_filepath_list, normalize, vocab), the same two console lines, and its __getitem__ (manifests interleaved by index).
+    Beyond the reference: `sample()` and the keywords partitions, seed, device_batches, resample and feature_fn of the
+    ManifestTaskDataset machinery -- for one seed the index and draw stream is that of SpectrogramDataset -- and audio_conf['noise_dir'] /
+    augment=True, which the reference's class accepts and ignores, work as on SpectrogramDataset, with the same rejections."""
+
+    def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
+                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False):
+        noise = _wav_dataset_options(self, audio_conf, feature_fn, augment, device_batches, resample, input_type, '157-165')
+        self.sample_rate = audio_conf.get('sample_rate', getattr(args, 'sample_rate', 16000))
+        fbank_geometry(self.sample_rate)                             # a rate beyond the 512-point transform is rejected here
+        self.normalize, self.augment, self.noise_prob = normalize, augment, audio_conf.get('noise_prob')
+        fe = []           # built at the first utterance: constructing the dataset must not need the device
+
+        def front_end():
+            if not fe:
+                fe.append(LogFBankFrontEnd(self.sample_rate, 80, self.normalize))
+            return fe[0]
+        if feature_fn is None:
+            def feature_fn(path):
+                return front_end()(load_wav_pcm16(path)).cpu()
+        super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
+        _wav_dataset_wiring(self, noise, augment, resample, device_batches, front_end, manifest_filepath_list, input_type)
+        self.max_size = max(len(ids) for ids in self.ids_list) * len(self.ids_list)      # :114-122: no 30000 rule in this class
+        print('max_size:', self.max_size)
+        print('input_type:', input_type)
+
+    def parse_transcript(self, transcript_path):
+        return parse_transcript(self.vocab, transcript_path)
+
+    def parse_audio(self, audio_path):
+        """utils/data_loader.py:145-155; with augmentation and / or a noise injector, this utterance's draws from the dataset's stream"""
+        draws = self._draws(1)
+        return self._feature(audio_path, None if draws is None else draws[0])
+
+    def __getitem__(self, index):
+        """utils/data_loader.py:133-143: the manifests interleaved by index, whatever is_train says"""
+        ids = self.ids_list[index % len(self.ids_list)]
+        row = ids[(index // len(self.ids_list)) % len(ids)]
+        draws = self._draws(1)
+        return self._feature(row[0], None if draws is None else draws[0])[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
 
 
 class NoiseInjection(object):

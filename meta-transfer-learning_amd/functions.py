@@ -17,13 +17,14 @@ from .model import Decoder, Encoder, Transformer
 
 def init_transformer_model(args, vocab, train=True, is_factorized=False, r=100):
     """Builds Encoder/Decoder/Transformer exactly like utils/functions.py:307-351, including the in-place derivation
-    of args.dim_input from the sample rate / window (161 bins -> 40 pooled rows x 128 channels = 5120)."""
+    of args.dim_input from the sample rate / window (161 bins -> 40 pooled rows x 128 channels = 5120), or 2560 for
+    feat='logfbank' (LogFBankFrontEnd / LogFBankDataset: 80 bands -> 20 pooled rows)."""
     if args.feat_extractor != 'vgg_cnn':
         raise NotImplementedError("only feat_extractor='vgg_cnn' is on the accelerated path")
     bins = int(math.floor((args.sample_rate * args.window_size) / 2) + 1)
     args.dim_input = int(math.floor(int(math.floor(bins) / 2) / 2)) * 128
     if getattr(args, 'feat', 'spectrogram') == 'logfbank':
-        raise NotImplementedError('logfbank features are outside the accelerated path')
+        args.dim_input = 2560                                        # :322-323: 80 bands pool to 20 rows of 128 channels
     encoder = Encoder(args.num_enc_layers, num_heads=args.num_heads, dim_model=args.dim_model, dim_key=args.dim_key,
                       dim_value=args.dim_value, dim_input=args.dim_input, dim_inner=args.dim_inner,
                       src_max_length=args.src_max_len, dropout=args.dropout, is_factorized=is_factorized, r=r)

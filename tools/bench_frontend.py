@@ -44,6 +44,19 @@ K = 16 ten-second utterances at 8 kHz (80 000 samples each) for a 16 kHz front-e
 plus the HIP-event time of mtl_resample alone and the bytes it reads and writes over that time, against the HBM rate.
 
     python tools/bench_frontend.py --resample --resample-out profiles/frontend_resample.json
+
+--logfbank [--logfbank-out PATH] runs the log-mel filterbank leg instead, same protocol, four paths that alternate
+over the K waveforms rounded to 16-bit values:
+
+  (a) batched:       one `LogFBankFrontEnd.batch(waves)`
+  (b) per utterance: K x `LogFBankFrontEnd.__call__(y).cpu()`, `collate`, `.to(device)`
+  (c) host:          the fp64 numpy restatement of the features per utterance on the calling thread, `collate`, `.to(device)`: what a
+                     user who wants the 80-band input does today
+  (d) spectrogram:   `SpectrogramFrontEnd.batch(waves)` on the same waveforms (161 bins)
+
+plus the HIP-event times of the two launches of mtl_fbank_batch and of mtl_spect_batch alone (operands already on the device).
+
+    python tools/bench_frontend.py --logfbank --logfbank-out profiles/frontend_logfbank.json
 """
 import argparse
 import json
@@ -78,6 +91,8 @@ def main():
     ap.add_argument('--augment-out', default=None)
     ap.add_argument('--resample', action='store_true')
     ap.add_argument('--resample-out', default=None)
+    ap.add_argument('--logfbank', action='store_true')
+    ap.add_argument('--logfbank-out', default=None)
     a = ap.parse_args()
     if a.reps < 20 or a.warmup < 3:
         ap.error('at least 20 timed calls after at least 3 warm-ups')
@@ -95,6 +110,8 @@ def main():
         return augment_leg(a, mtl_amd, _lib, fe, waves, labels)
     if a.resample or a.resample_out:
         return resample_leg(a, mtl_amd, _lib, fe, waves)
+    if a.logfbank or a.logfbank_out:
+        return logfbank_leg(a, mtl_amd, _lib, fe, waves, labels)
 
     def per_utterance():
         specs = [fe(y).cpu() for y in waves]
@@ -501,6 +518,137 @@ def resample_leg(a, mtl_amd, _lib, fe, waves16):
     print(json.dumps(res))
     if a.resample_out:
         with open(a.resample_out, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write('\n')
+
+
+def logfbank_leg(a, mtl_amd, _lib, fe, waves, labels):
+    K, dev = len(waves), fe.device
+    waves = [(np.rint(y.astype(np.float64) * 32768.0) / 32768.0).astype(np.float32) for y in waves]      # what a 16-bit file holds
+    fb = mtl_amd.LogFBankFrontEnd(fe.sample_rate, 80, normalize=True)
+    table = fb.filterbank
+
+    def host_features(y):
+        """the definition in fp64 numpy, normalised"""
+        s = 32768.0 * y.astype(np.float64)
+        p = s.copy()
+        p[1:] -= 0.97 * s[:-1]
+        T = int(mtl_amd.fbank_frames([len(y)], fe.sample_rate)[0])
+        padded = np.zeros((T - 1) * fb.fs + fb.fl)
+        padded[:len(p)] = p
+        frames = np.lib.stride_tricks.as_strided(padded, (T, fb.fl), (padded.strides[0] * fb.fs, padded.strides[0]))
+        spec = np.fft.rfft(frames, fb.nfft, axis=1)
+        E = table @ ((spec.real ** 2 + spec.imag ** 2) / fb.nfft).T
+        v = np.log(np.where(E == 0, mtl_amd.data.FBANK_EPS, E))
+        return torch.from_numpy(((v - v.mean()) / v.std(ddof=1)).astype(np.float32))
+
+    def batched():
+        return fb.batch(waves)[0]
+
+    def per_utterance():
+        return mtl_amd.data.collate([fb(y).cpu() for y in waves], labels)[0].to(dev)
+
+    def host():
+        return mtl_amd.data.collate([host_features(y) for y in waves], labels)[0].to(dev)
+
+    def spectrogram():
+        return fe.batch(waves)[0]
+
+    # the three filterbank paths must describe the same batch before their times are compared
+    xa, xb, xc = batched(), per_utterance(), host()
+    torch.cuda.synchronize()
+    assert xa.shape == xb.shape == xc.shape == (K, 1, 80, int(mtl_amd.fbank_frames([len(waves[0])], fe.sample_rate)[0])) and torch.equal(xa, xb)
+    vs_host = float((xa.double() - xc.double()).abs().max())              # (the largest is an ill-conditioned element: band 0, the DC bin)
+    vs_host_l2 = float((xa.double() - xc.double()).norm() / xc.double().norm())
+    assert vs_host_l2 < 1e-4, vs_host_l2
+
+    m = torch.randn(4096, 4096, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        m @ m
+    e0.record()
+    for _ in range(20):
+        m @ m
+    e1.record()
+    torch.cuda.synchronize()
+    chain = max(int(round(a.queued_ms / (e0.elapsed_time(e1) / 20))), 1)
+
+    def timed(fn, busy):
+        torch.cuda.synchronize()
+        if busy:
+            for _ in range(chain):
+                m @ m
+        t0 = time.perf_counter()
+        x = fn()
+        dt = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        del x
+        return dt
+
+    paths = (('batched', batched), ('per_utterance', per_utterance), ('host', host), ('spectrogram', spectrogram))
+    times = {(name, busy): [] for name, _ in paths for busy in (False, True)}
+    for rep in range(a.warmup + a.reps):
+        for busy in (False, True):
+            for name, fn in paths:
+                dt = timed(fn, busy)
+                if rep >= a.warmup:
+                    times[(name, busy)].append(dt)
+    host_features_ms = []
+    for rep in range(a.warmup + a.reps):
+        t0 = time.perf_counter()
+        [host_features(y) for y in waves]
+        if rep >= a.warmup:
+            host_features_ms.append(1e3 * (time.perf_counter() - t0))
+
+    # device time of the launches alone (operands on the device): the new kernel, and the spectrogram's on the same samples
+    lib = _lib.lib()
+    flat, offsets, frames, tmax = fb._pack(waves, None)
+    d_wav, d_off = torch.from_numpy(flat).to(dev), torch.from_numpy(offsets).to(dev)
+    out = torch.empty(K, 1, 80, tmax, device=dev)
+    ws_bytes = lib.mtl_fbank_batch_workspace(K)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    _, _, sframes, stmax = mtl_amd.pack_waveforms(waves, fe.hop, fe.n_fft)
+    sout = torch.empty(K, 1, fe.F, stmax, device=dev)
+    sws_bytes = lib.mtl_spect_batch_workspace(int(sframes.sum()), K, fe.F)
+    sws = torch.empty(sws_bytes // 8, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def fbank_launch():
+        _lib.check(lib.mtl_fbank_batch(st, d_wav.data_ptr(), d_off.data_ptr(), K, fb.fl, fb.fs, fb.nfft, fb.basis.data_ptr(), fb.ldb, fb.nfilt,
+                                       fb.band.data_ptr(), fb.band_w.data_ptr(), fb.band_w.numel(), out.data_ptr(), tmax, 1, ws.data_ptr(),
+                                       ws_bytes), 'mtl_fbank_batch')
+
+    def spect_launch():
+        _lib.check(lib.mtl_spect_batch(st, d_wav.data_ptr(), d_off.data_ptr(), K, fe.n_fft, fe.hop, fe.basis.data_ptr(), fe.ldb, fe.F,
+                                       sout.data_ptr(), stmax, 1, sws.data_ptr(), sws_bytes), 'mtl_spect_batch')
+    launch_us = {'fbank': [], 'spect': []}
+    for rep in range(a.warmup + a.reps):
+        for name, fn in (('fbank', fbank_launch), ('spect', spect_launch)):
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                launch_us[name].append(1e3 * e0.elapsed_time(e1))
+    assert torch.equal(out, xa)
+
+    key = lambda n, b: '%s_%s' % (n, 'busy' if b else 'idle')
+    flop = 2.0 * int(frames.sum()) * 2 * (fb.nfft // 2 + 1) * fb.fl
+    res = dict(device=torch.cuda.get_device_name(0), utterances=K, samples_per_utterance=len(waves[0]), frames_per_utterance=int(frames[0]),
+               spectrogram_frames_per_utterance=int(sframes[0]), reps=a.reps, warmup=a.warmup, queued_ms=a.queued_ms, queued_products=chain,
+               batched_equals_per_utterance=True, worst_abs_batched_vs_host_fp64_normalised=vs_host, rel_l2_batched_vs_host_fp64_normalised=vs_host_l2,
+               utt_per_s={key(n, b): K / statistics.median(v) for (n, b), v in times.items()},
+               call_ms_median={key(n, b): 1e3 * statistics.median(v) for (n, b), v in times.items()},
+               call_ms_min_max={key(n, b): [1e3 * min(v), 1e3 * max(v)] for (n, b), v in times.items()},
+               host_features_ms_median=statistics.median(host_features_ms),
+               fbank_launches_us_median=statistics.median(launch_us['fbank']), fbank_launches_us_min=min(launch_us['fbank']),
+               spect_launches_us_median=statistics.median(launch_us['spect']), spect_launches_us_min=min(launch_us['spect']),
+               fbank_dft_gflop=flop / 1e9, fbank_dft_tflops=flop / (statistics.median(launch_us['fbank']) * 1e-6) / 1e12,
+               output_elements=dict(logfbank=int(out.numel()), spectrogram=int(sout.numel())))
+    print(json.dumps(res))
+    if a.logfbank_out:
+        with open(a.logfbank_out, 'w') as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write('\n')
 
