@@ -580,6 +580,35 @@ int mtl_lstm_stack_fwd(void* stream, const mtl_lstm_stack* layers, float mscale,
 int mtl_lstm_stack_bwd(void* stream, const mtl_lstm_stack* layers, const float* dx_up, float mscale, float* scratch, int T, int B, int H,
                        int NL, void* workspace);
 
+/* ---- GRU (csrc/mtl_gru.hip; lm/model/rnn_model.py:21 nn.GRU, `--model GRU`) -------------------------------------------------------
+ * torch gate order r | z | n.  gx = x_t . W_ih^T + b_ih and gh = h_{t-1} . W_hh^T + b_hh come from mtl_gemm_f32_ex (B x 3H each):
+ *   r = sigmoid(gx_r + gh_r), z = sigmoid(gx_z + gh_z), q = gh_n, n = tanh(gx_n + r q), h = (1 - z) n + z h_prev.
+ * One time step, element-wise (any B H):
+ *   forward : acts (B x 4H) = r | z | n | q (saved), h, h_drop (nullable) = h [* mask * mscale] as in mtl_lstm_cell_fwd.
+ *   backward: dh = dh_up [* mask * mscale] + dh_rec + carry_in (all three nullable; the last step has neither dh_rec nor carry_in);
+ *             dn = dh (1 - z), dz = dh (h_prev - n), da_n = dn (1 - n^2), dq = da_n r, da_r = da_n q r (1 - r), da_z = dz z (1 - z);
+ *             dgx (B x 3H) = da_r | da_z | da_n  (-> W_ih, b_ih, the input gradient), dgh (B x 3H) = da_r | da_z | dq  (-> W_hh, b_hh,
+ *             dh_rec of the step before), carry_out (B x H) = dh z  (straight to the same unit of the step before; may alias carry_in). */
+int mtl_gru_cell_fwd(void* stream, const float* gx, const float* gh, const float* h_prev, float* acts, float* h, float* h_drop,
+                     const unsigned char* mask, float mscale, int B, int H);
+int mtl_gru_cell_bwd(void* stream, const float* dh_up, const unsigned char* mask, float mscale, const float* dh_rec,
+                     const float* carry_in, const float* acts, const float* h_prev, float* dgx, float* dgh, float* carry_out, int B,
+                     int H);
+/* Persistent GRU layer: ALL T time steps of one layer in one launch per direction, with the ownership, the hand-off and the workspace
+ * of the persistent LSTM layer (above): workgroup w owns hidden units [8 w, 8 w + 8), its 24 gate rows of W_hh stay in registers, one
+ * grid-wide hand-off per step, bounded spins, sticky error word u32 [1] of the workspace.
+ *   forward : gx (T B, 3H) of all steps, hall (T + 1, B, H) with slot 0 = the incoming state; writes hall[1..T], acts (T B, 4H) = r|z|n|q
+ *             and xout (T B, H, nullable) -- what T calls of the recurrent product + mtl_gru_cell_fwd produce.
+ *   backward: dx_up (T B, H) gradient of xout (may be NULL); writes dgx and dgh (T B, 3H each) of every step (truncated BPTT: no gradient
+ *             into the incoming state) -- what T calls of mtl_gru_cell_bwd + the dh_rec product produce.
+ * workspace: mtl_lstm_layer_workspace() bytes, the LSTM launches' own (launches on one stream share it).
+ * mtl_gru_layer_supported: the shapes of mtl_lstm_layer_supported. */
+int mtl_gru_layer_supported(int B, int H);
+int mtl_gru_layer_fwd(void* stream, const float* gx, const float* w_hh, const float* b_hh, float* hall, float* acts, float* xout,
+                      const unsigned char* mask, float mscale, int T, int B, int H, void* workspace);
+int mtl_gru_layer_bwd(void* stream, const float* dx_up, const unsigned char* mask, float mscale, const float* w_hh, const float* acts,
+                      const float* hall, float* dgx, float* dgh, int T, int B, int H, void* workspace);
+
 /* ---- LM sequence NLL (csrc/mtl_lstm.hip; utils/lm.py:42-155 LM.evaluate: LM rescoring of finished beam hypotheses) ------------
  * x (R x H, leading dimension ldx): the top LSTM layer's outputs, rows ordered (t, b) with R = T B; W (V x H), bias (V, nullable):
  * the vocabulary projection (decoder.weight / decoder.bias); target (R) int64, < 0 = skipped row.

@@ -140,6 +140,11 @@ SIGNATURES = {
     'mtl_lstm_stack_scratch': (L, [I, I, I, I]),
     'mtl_lstm_stack_fwd': (I, [P, P, F, I, I, I, I, P]),
     'mtl_lstm_stack_bwd': (I, [P, P, P, F, P, I, I, I, I, P]),
+    'mtl_gru_cell_fwd': (I, [P, P, P, P, P, P, P, P, F, I, I]),
+    'mtl_gru_cell_bwd': (I, [P, P, P, F, P, P, P, P, P, P, P, I, I]),
+    'mtl_gru_layer_supported': (I, [I, I]),
+    'mtl_gru_layer_fwd': (I, [P, P, P, P, P, P, P, P, F, I, I, I, P]),
+    'mtl_gru_layer_bwd': (I, [P, P, P, F, P, P, P, P, P, I, I, I, P]),
     'mtl_lm_nll_workspace': (L, [I, I]),
     'mtl_lm_nll_fwd': (I, [P, P, I, P, P, P, I, I, I, I, P, P, P, L]),
     'mtl_beam_state_words': (L, [I, I, I]),

@@ -15,19 +15,11 @@
 //     so all of them are resident.
 // The backward runs the same ownership in reverse time (see lstm_layer_bwd_kernel).  The weight gradients remain three products
 // over all T steps (lm.py).  Reductions are fixed-order: bitwise reproducible.
-#include "mtl_common.h"
-#include "../../include/mtl_hip.h"
+#include "mtl_handoff.h"      // LU, SPIN_LIMIT, HDR, PBUF, grid_wait / grid_arrive / store_shared (shared with mtl_gru.hip)
 
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int LU = 8;                        // hidden units per workgroup
-constexpr unsigned SPIN_LIMIT = 1u << 22;    // polls before a wait gives up (~seconds): sets the error word
-constexpr int HDR = 1024;                    // workspace header in 4-byte words: [0] arrival counter (single-layer kernels), [1] error word,
-                                             // [64 + 64 g ..): the per-workgroup step flags of group g of the stack kernels
-constexpr int MAXL = MTL_LSTM_MAX_LAYERS;
-constexpr long PBUF = 64L * 32 * 512;        // largest [nwg][B][H] partial buffer, floats
 
 struct LstmP {
     const float *gx, *whh, *bhh;
@@ -41,29 +33,7 @@ struct LstmP {
     float* dG;
 };
 
-// Hand-off without cache maintenance (guide, Guideline 16 form R1): the payload that crosses workgroups (h_t, dG_t) is stored
-// write-through (relaxed agent-scope atomic stores = `global_store ... sc1`) and read with `sc1` loads (relaxed agent-scope atomic
-// loads: served below the reader's L1), so neither an L2 write-back (release fence, 2-6 us with fresh dirty lines) nor an L1
-// invalidate (acquire fence, 1.7 us) is paid per step; the flag follows the payload behind `s_waitcnt vmcnt(0)`.
-__device__ __forceinline__ void grid_wait(unsigned* sync, unsigned target) {
-    if (threadIdx.x == 0) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(&sync[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            if (++spins > SPIN_LIMIT) {
-                __hip_atomic_store(&sync[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void grid_arrive(unsigned* sync) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's write-through stores are acknowledged
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(&sync[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
+// (the hand-off itself -- grid_wait / grid_arrive / store_shared -- is in mtl_handoff.h)
 // B x H floats written by other workgroups -> LDS (same linear layout), 256 threads.  16-byte `sc1` loads issued back to back with ONE
 // wait: the relaxed agent-scope atomic loads of HIP (`__hip_atomic_load`) are kept in program order by the compiler -- a wait after every
 // load -- which made this copy a chain of 20 memory round trips (5.0 us of a 13.6 us step, measured with s_memrealtime stamps;
@@ -95,8 +65,6 @@ __device__ __forceinline__ void load_shared_x4(const float* q, long stride, floa
     asm volatile("global_load_dword %0, %1, off sc1" : "=v"(v[3]) : "v"(q + 3 * stride) : "memory");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
-
-__device__ __forceinline__ void store_shared(float* q, float v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 template <int KC>      // H = 8 KC
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void lstm_layer_fwd_kernel(LstmP p) {

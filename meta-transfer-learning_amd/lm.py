@@ -1,12 +1,14 @@
 """LM meta-transfer path on the MI355X (BASELINE.json configs[4]): drop-in pieces for `lm/model/rnn_model.py`,
 `lm/util/data.py` and the training loop of `lm/main_meta_transfer.py:277-411`.
 
-* `RNNModel('LSTM', ntoken, ninp, nhid, nlayers, dropout)`: same constructor, parameter names (`encoder.weight`,
+* `RNNModel('LSTM' | 'GRU', ntoken, ninp, nhid, nlayers, dropout, tie_weights)`: same constructor, parameter names (`encoder.weight`,
   `rnn.weight_ih_l0`, ..., `decoder.bias`), `init_weights` and RNG draw order as the reference (bit-identical initialisation); all
   parameters are views into ONE flat fp32 buffer, the compute runs in libmtl_hip.so (`LMEngine`): embedding gather + Philox dropout,
   per layer ONE GEMM for the input contributions of all T steps, per step the recurrent GEMM (small-product engine) + the fused
   LSTM cell kernel, vocabulary projection + fused cross-entropy; hand-written backward (BPTT over the bptt window), weight
-  gradients as three products over all T steps with the bias gradients folded in.
+  gradients as three products over all T steps with the bias gradients folded in.  A GRU (csrc/mtl_gru.hip) carries a single hidden
+  tensor and has two gate-gradient tensors per layer; `tie_weights=True` makes `decoder.weight` the `encoder.weight` Parameter (one
+  entry in the flat layout, both gradients accumulate into it).  `RNN_TANH` / `RNN_RELU` raise.
 * `LMDataset`: `batchify` / `get_batch` / `sample(manifest_id, i)` with the reference's offsets.
 * `LMMetaTrainer`: the meta step.  The reference's loop cannot run on torch >= 2 (it back-propagates through parameter storage it
   has overwritten, see oracle/lm_refimpl.py), so the semantics implemented are the documented first-order reading: per task
@@ -40,12 +42,19 @@ def synth_corpus(seed, ntoken, length):
 class RNNModel(nn.Module):
     def __init__(self, rnn_type, ntoken, ninp, nhid, nlayers, dropout=0.5, tie_weights=False):
         super().__init__()
-        if rnn_type != 'LSTM' or tie_weights:
-            raise NotImplementedError("accelerated LM path: rnn_type='LSTM', untied weights")
+        if rnn_type not in ('LSTM', 'GRU'):
+            raise NotImplementedError("accelerated LM path: rnn_type 'LSTM' or 'GRU' (got %r)" % (rnn_type,))
         self.drop = nn.Dropout(dropout)
         self.encoder = nn.Embedding(ntoken, ninp)
-        self.rnn = nn.LSTM(ninp, nhid, nlayers, dropout=dropout)            # parameter container only (same init draws)
+        self.rnn = getattr(nn, rnn_type)(ninp, nhid, nlayers, dropout=dropout)   # parameter container only (same init draws)
         self.decoder = nn.Linear(nhid, ntoken)
+        if tie_weights:
+            # (lm/model/rnn_model.py:38-41) ONE Parameter under both names: named_parameters() and the flat layout list it once, as
+            # encoder.weight; state_dict() keeps both keys
+            if nhid != ninp:
+                raise ValueError('When using the tied flag, nhid must be equal to emsize')
+            self.decoder.weight = self.encoder.weight
+        self.tie_weights = bool(tie_weights)
         self.rnn_type, self.ntoken, self.ninp, self.nhid, self.nlayers, self.dropout_rate = rnn_type, ntoken, ninp, nhid, nlayers, dropout
         self.init_weights()
         self._layout = ParamLayout([(n, p.shape) for n, p in self.named_parameters()])
@@ -85,7 +94,10 @@ class RNNModel(nn.Module):
         return self._gflat
 
     def init_hidden(self, bsz):
+        """(h, c) for an LSTM, a single tensor for a GRU (lm/model/rnn_model.py:64-70)"""
         dev = self._theta.device
+        if self.rnn_type == 'GRU':
+            return torch.zeros(self.nlayers, bsz, self.nhid, device=dev)
         return (torch.zeros(self.nlayers, bsz, self.nhid, device=dev), torch.zeros(self.nlayers, bsz, self.nhid, device=dev))
 
     def _need_engine(self):
@@ -103,23 +115,28 @@ class RNNModel(nn.Module):
 
 
 class LMEngine:
-    """Forward + hand-written backward of the LSTM LM as library calls on the current stream (rows are ordered (t, b))."""
+    """Forward + hand-written backward of the LSTM / GRU LM as library calls on the current stream (rows are ordered (t, b))."""
 
     def __init__(self, model, device):
         self.m, self.device, self.lib, self.L = model, device, _lib.lib(), model._layout
         self.pool, self.saved = {}, None
         self.ws = torch.empty(4 << 20, dtype=torch.float32, device=device)
-        # all T steps of a layer in ONE launch per direction (csrc/mtl_lstm.hip) where the shape is supported; False keeps the per-step
-        # recurrent product + cell kernel (tests compare the two; unsupported shapes take it anyway)
+        # all T steps of a layer in ONE launch per direction (csrc/mtl_lstm.hip, csrc/mtl_gru.hip) where the shape is supported; False
+        # keeps the per-step recurrent product + cell kernel (tests compare the two; unsupported shapes take it anyway)
         self.persistent = True
-        # the whole stack as one wavefront launch per direction (layers one step apart); False: one launch per layer and direction
+        # LSTM only: the whole stack as one wavefront launch per direction (layers one step apart); False: one launch per layer and
+        # direction (a GRU always runs one launch per layer and direction)
         self.stacked = True
         self.sync_ws = torch.zeros(int(self.lib.mtl_lstm_layer_workspace()) // 4, dtype=torch.int32, device=device)
         self._persistent_issued = False
 
+    def off(self, name):
+        """offset of a parameter in the flat buffers; a tied model holds ONE tensor for encoder.weight and decoder.weight"""
+        return self.L.off('encoder.weight' if (name == 'decoder.weight' and self.m.tie_weights) else name)
+
     def check_handoff(self):
-        """The persistent LSTM kernels bound every grid-wide wait and set a sticky error word instead of hanging the device (e.g.
-        when their workgroups could not all become resident).  Called wherever results leave the engine: RNNModel.forward
+        """The persistent LSTM / GRU kernels bound every grid-wide wait and set a sticky error word instead of hanging the device
+        (e.g. when their workgroups could not all become resident).  Called wherever results leave the engine: RNNModel.forward
         (evaluation / inference), LMMetaTrainer.run_iteration, and by direct LMEngine users through results().  One 4-byte
         read-back (a host sync) -- skipped when no persistent launch has been issued since the last check."""
         if not self._persistent_issued:
@@ -127,8 +144,8 @@ class LMEngine:
         self._persistent_issued = False
         if int(self.sync_ws[1]) != 0:
             self.sync_ws[1] = 0
-            raise RuntimeError('mtl_lstm: a grid-wide wait of a persistent LSTM launch timed out; its results are invalid '
-                               '(LMEngine.stacked = False / LMEngine.persistent = False select the per-layer / per-step launches)')
+            raise RuntimeError('mtl_lstm / mtl_gru: a grid-wide wait of a persistent recurrent-layer launch timed out; its results are '
+                               'invalid (LMEngine.stacked = False / LMEngine.persistent = False select the per-layer / per-step launches)')
 
     def buf(self, name, shape, dtype=torch.float32):
         key = (name, tuple(int(v) for v in shape), dtype)
@@ -160,14 +177,14 @@ class LMEngine:
         return torch.stack([first, nxt])
 
     def forward(self, theta, x, y, hidden, dropout_p=0.0):
-        """x (T, B) int64, y (T*B) int64 or None, hidden (h, c) each (L, B, H).  -> dict(logits (T*B, V), loss (1,) or None,
-        hidden (detached new state))."""
+        """x (T, B) int64, y (T*B) int64 or None, hidden (h, c) each (L, B, H) -- for a GRU the single tensor h.  -> dict(logits
+        (T*B, V), loss (1,) or None, hidden (detached new state, in the form it came in))."""
         rec = self._recurrent(theta, x, hidden, dropout_p)
-        m, lib, st, Lo = self.m, self.lib, self.stream, self.L
+        m, lib, st = self.m, self.lib, self.stream
         T, B, xin = rec['T'], rec['B'], rec['last']
         R, H, V = T * B, m.nhid, m.ntoken
         P = theta.data_ptr()
-        o = lambda n: P + 4 * Lo.off(n)
+        o = lambda n: P + 4 * self.off(n)
         logits = self.buf('logits', (R, V))
         self.gemm(0, 1, R, V, H, xin.data_ptr(), H, o('decoder.weight'), H, logits.data_ptr(), V, bias=o('decoder.bias'))
         loss = None
@@ -178,11 +195,11 @@ class LMEngine:
             check(lib.mtl_ce_argmax_fwd(st, logits.data_ptr(), gold.data_ptr(), R, V, V, -1, 0.0, R, None, lse.data_ptr(), hyp.data_ptr(),
                                         rowloss.data_ptr(), loss.data_ptr()), 'ce_fwd')     # nn.CrossEntropyLoss(): mean over all T*B rows
         self.saved = dict(theta=theta, **rec)
-        return dict(logits=logits, loss=loss, hidden=(rec['hn'].clone(), rec['cn'].clone()))
+        return dict(logits=logits, loss=loss, hidden=rec['hn'].clone() if rec['cn'] is None else (rec['hn'].clone(), rec['cn'].clone()))
 
     def sequence_nll(self, theta, ids, targets):
         """Summed next-word NLL of a ragged batch (LM rescoring, utils/lm.py:112-136 of the reference, batched): ids (T, B) int64,
-        targets (T, B) int64 with -1 after a sequence's end.  Eval-mode forward from the zero state (the LSTM is causal: the padding
+        targets (T, B) int64 with -1 after a sequence's end.  Eval-mode forward from the zero state (the LSTM / GRU is causal: the padding
         after a sequence's end cannot change its valid positions), then ONE fused vocabulary projection + log-sum-exp
         (mtl_lm_nll_fwd; the T B x V logits are never written).  -> seq_nll (B,) fp32 on the device.  Reuses forward()'s buffers:
         a pending backward() is invalidated."""
@@ -194,7 +211,7 @@ class LMEngine:
         self.saved = None
         zero = self.buf('nll_h0', (NL, B, H))
         zero.zero_()
-        rec = self._recurrent(theta, ids, (zero, zero), 0.0)
+        rec = self._recurrent(theta, ids, zero if m.rnn_type == 'GRU' else (zero, zero), 0.0)
         self.saved = None
         tgt = self.buf('nll_tgt', (R,), torch.int64)
         tgt.copy_(targets.detach().reshape(-1).to(torch.int64), non_blocking=True)
@@ -202,7 +219,7 @@ class LMEngine:
         need = int(lib.mtl_lm_nll_workspace(R, V))
         ws = self.ws if need <= self.ws.numel() * 4 else self.buf('nll_ws', ((need + 3) // 4,))
         P = theta.data_ptr()
-        check(lib.mtl_lm_nll_fwd(self.stream, rec['last'].data_ptr(), H, P + 4 * self.L.off('decoder.weight'), P + 4 * self.L.off('decoder.bias'),
+        check(lib.mtl_lm_nll_fwd(self.stream, rec['last'].data_ptr(), H, P + 4 * self.off('decoder.weight'), P + 4 * self.off('decoder.bias'),
                                  tgt.data_ptr(), R, H, V, B, row.data_ptr(), seq.data_ptr(), ws.data_ptr(), ws.numel() * 4), 'mtl_lm_nll_fwd')
         self.check_handoff()          # the caller ranks hypotheses by these values
         return seq.clone()
@@ -210,11 +227,12 @@ class LMEngine:
     def _recurrent(self, theta, x, hidden, dropout_p):
         """the recurrent half of forward(): embedding (+ dropout) and the LSTM stack over x (T, B) from `hidden` -> dict with the top
         layer's (dropped) output `last` (T B, H) and what backward() needs"""
-        m, lib, st, Lo = self.m, self.lib, self.stream, self.L
+        m, lib, st = self.m, self.lib, self.stream
         T, B = int(x.shape[0]), int(x.shape[1])
         R, H, E, V, NL = T * B, m.nhid, m.ninp, m.ntoken, m.nlayers
+        gru = m.rnn_type == 'GRU'
         P = theta.data_ptr()
-        o = lambda n: P + 4 * Lo.off(n)
+        o = lambda n: P + 4 * self.off(n)
         # token ids and the occurrence chains of the embedding scatter-add: where the batch already lives (a device batch is indexed
         # with device ops -- a read-back here would drain the stream once per pass and leave the GPU idle while the host enqueues)
         xh = x.detach().to(torch.int64).contiguous()
@@ -241,12 +259,17 @@ class LMEngine:
             self._zpe_ok = (R, E)
         # with E == H the inputs of the weight-gradient products -- per layer x_l (R x H) and the previous states hall_l[:T] (R x H)
         # -- live in ONE arena [layer][x, hall] with constant strides, and the gate gradients in one [layer] stack: backward() then
-        # forms all 2 NL weight gradients (+ bias gradients) with a single batched product instead of 2 NL small ones
-        arena = self.buf('wg_arena', (NL, 2, (T + 1) * B * H)) if (E == H and NL > 1) else None
+        # forms all 2 NL weight gradients (+ bias gradients) with a single batched product instead of 2 NL small ones (LSTM only: a
+        # GRU's two gate-gradient tensors differ, see _gru_backward)
+        arena = self.buf('wg_arena', (NL, 2, (T + 1) * B * H)) if (E == H and NL > 1 and not gru) else None
         emb = arena[0, 0, :R * E].view(R, E) if arena is not None else self.buf('emb', (R, E))
         m_emb = mask('m_emb', R * E, 1)
         check(lib.mtl_embed_pe_fwd(st, ids.data_ptr(), o('encoder.weight'), zpe.data_ptr(), emb.data_ptr(), R, R, E,
                                    m_emb.data_ptr() if m_emb is not None else None, sc), 'embed')
+        if gru:
+            layers, last, hn, fused = self._gru_forward(o, hidden, emb, mask, sc, T, B)
+            return dict(T=T, B=B, layers=layers, last=last, m_emb=m_emb, sc=sc, ids=ids, chains=chains, stacked=False, arena=None, hn=hn,
+                        cn=None, fused=fused)
         h0, c0 = hidden
         layers = []
         xin, kin = emb, E
@@ -298,9 +321,79 @@ class LMEngine:
             cn[l].copy_(layers[l]['call'][T])
         return dict(T=T, B=B, layers=layers, last=xin, m_emb=m_emb, sc=sc, ids=ids, chains=chains, stacked=stacked, arena=arena, hn=hn, cn=cn)
 
+    def _gru_forward(self, o, hidden, emb, mask, sc, T, B):
+        """the GRU stack of _recurrent() (csrc/mtl_gru.hip): per layer ONE product for the input contributions of all T steps (T B x 3H,
+        gates r | z | n), then ONE persistent launch for the T steps -- or, for unsupported shapes / persistent = False, per step the
+        recurrent product + the cell kernel.  Saved per step: r | z | n | q (T B x 4H).  -> (layers, last, hn, persistent launches ran)"""
+        m, lib, st = self.m, self.lib, self.stream
+        R, H, NL = T * B, m.nhid, m.nlayers
+        fused = self.persistent and bool(lib.mtl_gru_layer_supported(B, H))
+        layers, hn = [], self.buf('hn', (NL, B, H))
+        xin, kin = emb, m.ninp
+        for l in range(NL):
+            hall = self.buf('hall%d' % l, (T + 1, B, H))
+            hall[0].copy_(hidden[l])
+            acts, xout, gx = self.buf('acts%d' % l, (R, 4 * H)), self.buf('xout%d' % l, (R, H)), self.buf('gru_gx', (R, 3 * H))
+            msk = mask('m_l%d' % l, R * H, 2 + l)
+            mp = msk.data_ptr() if msk is not None else None
+            whh, bhh = o('rnn.weight_hh_l%d' % l), o('rnn.bias_hh_l%d' % l)
+            layers.append(dict(x=xin, kin=kin, hall=hall, acts=acts, mask=msk))
+            self.gemm(0, 1, R, 3 * H, kin, xin.data_ptr(), kin, o('rnn.weight_ih_l%d' % l), kin, gx.data_ptr(), 3 * H, bias=o('rnn.bias_ih_l%d' % l))
+            if fused:
+                self._persistent_issued = True
+                check(lib.mtl_gru_layer_fwd(st, gx.data_ptr(), whh, bhh, hall.data_ptr(), acts.data_ptr(), xout.data_ptr(), mp, sc, T, B, H,
+                                            self.sync_ws.data_ptr()), 'gru_layer_fwd')
+            gh = self.buf('gru_gh', (B, 3 * H))
+            for t in range(0 if fused else T):
+                self.gemm(0, 1, B, 3 * H, H, hall[t].data_ptr(), H, whh, H, gh.data_ptr(), 3 * H, bias=bhh)
+                check(lib.mtl_gru_cell_fwd(st, gx.data_ptr() + 12 * t * B * H, gh.data_ptr(), hall[t].data_ptr(), acts.data_ptr() + 16 * t * B * H,
+                                           hall[t + 1].data_ptr(), xout.data_ptr() + 4 * t * B * H, mp + t * B * H if mp is not None else None,
+                                           sc, B, H), 'gru_cell_fwd')
+            hn[l].copy_(hall[T])
+            xin, kin = xout, H
+        return layers, xin, hn, fused
+
+    def _gru_backward(self, S, dx, o, g):
+        """the GRU stack of backward(): dx = gradient of the top layer's (dropped) output -> gradient of the embedding output.  Per
+        layer the gate gradients of all steps as TWO (T B x 3H) tensors -- dgx = [da_r, da_z, da_n] (input side) and dgh = [da_r, da_z,
+        dq] (recurrent side): they differ in their last third, so bias_ih and bias_hh get different gradients -- then two products
+        per layer for the weight (+ bias) gradients, issued in a fixed order on the stream (deterministic), and one for the input
+        gradient."""
+        m, lib, st = self.m, self.lib, self.stream
+        T, B, sc = S['T'], S['B'], S['sc']
+        R, H, NL = T * B, m.nhid, m.nlayers
+        dgx, dgh = self.buf('gru_dgx', (R, 3 * H)), self.buf('gru_dgh', (R, 3 * H))
+        for l in reversed(range(NL)):
+            Ly = S['layers'][l]
+            kin, hall, acts = Ly['kin'], Ly['hall'], Ly['acts']
+            mp = Ly['mask'].data_ptr() if Ly['mask'] is not None else None
+            whh = o('rnn.weight_hh_l%d' % l)
+            if S['fused']:
+                self._persistent_issued = True
+                check(lib.mtl_gru_layer_bwd(st, dx.data_ptr(), mp, sc, whh, acts.data_ptr(), hall.data_ptr(), dgx.data_ptr(), dgh.data_ptr(),
+                                            T, B, H, self.sync_ws.data_ptr()), 'gru_layer_bwd')
+            dh_rec, carry = self.buf('dh_rec', (B, H)), self.buf('gru_carry', (B, H))
+            for t in reversed(range(0 if S['fused'] else T)):
+                first = t == T - 1
+                check(lib.mtl_gru_cell_bwd(st, dx.data_ptr() + 4 * t * B * H, mp + t * B * H if mp is not None else None, sc,
+                                           None if first else dh_rec.data_ptr(), None if first else carry.data_ptr(),
+                                           acts.data_ptr() + 16 * t * B * H, hall[t].data_ptr(), dgx.data_ptr() + 12 * t * B * H,
+                                           dgh.data_ptr() + 12 * t * B * H, carry.data_ptr(), B, H), 'gru_cell_bwd')
+                if t > 0:
+                    self.gemm(0, 0, B, H, 3 * H, dgh.data_ptr() + 12 * t * B * H, 3 * H, whh, H, dh_rec.data_ptr(), H)
+            self.gemm(1, 0, 3 * H, H, R, dgh.data_ptr(), 3 * H, hall.data_ptr(), H, g('rnn.weight_hh_l%d' % l), H, flags=ACCUM,
+                      rowsum=g('rnn.bias_hh_l%d' % l))
+            self.gemm(1, 0, 3 * H, kin, R, dgx.data_ptr(), 3 * H, Ly['x'].data_ptr(), kin, g('rnn.weight_ih_l%d' % l), kin, flags=ACCUM,
+                      rowsum=g('rnn.bias_ih_l%d' % l))
+            dxin = self.buf('dx_in%d' % l, (R, kin))
+            self.gemm(0, 0, R, kin, 3 * H, dgx.data_ptr(), 3 * H, o('rnn.weight_ih_l%d' % l), kin, dxin.data_ptr(), kin)
+            dx = dxin
+        return dx
+
     def backward(self, grad, scale=1.0):
         """grad (flat) += scale * dLoss/dtheta of the last forward (truncated BPTT over the window: no gradient into the incoming
-        hidden state, which the reference detaches with repackage_hidden)."""
+        hidden state, which the reference detaches with repackage_hidden).  Tied weights: the projection's weight gradient and the
+        embedding scatter-add accumulate into the one gradient tensor, in stream order."""
         S = self.saved
         if S is None:
             raise RuntimeError('backward() without a preceding forward() with targets')
@@ -308,8 +401,8 @@ class LMEngine:
         T, B, sc = S['T'], S['B'], S['sc']
         R, H, E, V, NL = T * B, m.nhid, m.ninp, m.ntoken, m.nlayers
         P, G = S['theta'].data_ptr(), grad.data_ptr()
-        o = lambda n: P + 4 * Lo.off(n)
-        g = lambda n: G + 4 * Lo.off(n)
+        o = lambda n: P + 4 * self.off(n)
+        g = lambda n: G + 4 * self.off(n)
         ldd = (V + 3) // 4 * 4
         dlog = self.buf('dlog', (R, ldd))
         check(lib.mtl_ce_bwd(st, self.pool[('logits', (R, V), torch.float32)].data_ptr(), self.pool[('lse', (R,), torch.float32)].data_ptr(),
@@ -319,6 +412,9 @@ class LMEngine:
         self.gemm(1, 0, V, H, R, dlog.data_ptr(), ldd, last.data_ptr(), H, g('decoder.weight'), H, flags=ACCUM, rowsum=g('decoder.bias'))
         dx = self.buf('dx_out', (R, H))
         self.gemm(0, 0, R, H, V, dlog.data_ptr(), ldd, o('decoder.weight'), H, dx.data_ptr(), H)
+        if m.rnn_type == 'GRU':
+            self._embed_backward(S, self._gru_backward(S, dx, o, g), g)
+            return
         stacked, arena = S['stacked'], S['arena']
         dGs = self.buf('dG_all', (NL, R, 4 * H))
         if stacked:
@@ -378,9 +474,14 @@ class LMEngine:
             dxin = self.buf('dx_in%d' % l, (R, kin))
             self.gemm(0, 0, R, kin, 4 * H, dG.data_ptr(), 4 * H, o('rnn.weight_ih_l%d' % l), kin, dxin.data_ptr(), kin)
             dx = dxin
+        self._embed_backward(S, dx, g)
+
+    def _embed_backward(self, S, dx, g):
+        """dx (T B, E) = gradient of the (dropped) embedding output -> scatter-add into encoder.weight's gradient, duplicates in row order"""
         m_emb = S['m_emb']
-        check(lib.mtl_embed_bwd(st, S['ids'].data_ptr(), S['chains'][0].data_ptr(), S['chains'][1].data_ptr(), dx.data_ptr(),
-                                g('encoder.weight'), R, E, -1, m_emb.data_ptr() if m_emb is not None else None, sc), 'embed_bwd')
+        check(self.lib.mtl_embed_bwd(self.stream, S['ids'].data_ptr(), S['chains'][0].data_ptr(), S['chains'][1].data_ptr(), dx.data_ptr(),
+                                     g('encoder.weight'), S['T'] * S['B'], self.m.ninp, -1, m_emb.data_ptr() if m_emb is not None else None,
+                                     S['sc']), 'embed_bwd')
 
 
 class LMDataset(object):
