@@ -1,16 +1,16 @@
 // GRU kernels for gfx950 (MI355X): the cell of one time step (element-wise) and the persistent layer -- all T time steps of one layer
 // in ONE launch per direction (lm/model/rnn_model.py:21 nn.GRU over a bptt window, `--model GRU`).
 //
-// torch gate order r | z | n.  With gx = x W_ih^T + b_ih (one product over all steps) and gh = h W_hh^T + b_hh:
-//   r = sigmoid(gx_r + gh_r)   z = sigmoid(gx_z + gh_z)   q = gh_n   n = tanh(gx_n + r q)   h' = (1 - z) n + z h
-// backward, dh' = masked gradient from above + recurrent gradient + direct carry:
-//   dn = dh' (1 - z)   dz = dh' (h - n)   carry = dh' z   da_n = dn (1 - n^2)   dq = da_n r   da_r = da_n q r (1 - r)   da_z = dz z (1 - z)
+// The cell arithmetic (gru_cell_act / gru_cell_grad, torch gate order r | z | n, q = gh_n saved as the fourth activation) is in
+// mtl_rnn_cell.h.  The kernels write two gate-gradient tensors:
 //   dgx = [da_r, da_z, da_n] (-> W_ih, b_ih, the input gradient)   dgh = [da_r, da_z, dq] (-> W_hh, b_hh, dh_rec(t - 1) = dgh W_hh)
 //
-// The persistent kernels keep the ownership, the hand-off (mtl_handoff.h) and the workspace of the LSTM's (mtl_lstm.hip): workgroup w
-// owns the hidden units [8 w, 8 w + 8) for the whole sequence, its 24 rows of W_hh (rows g H + j) stay in registers, one grid-wide
-// hand-off per step, fixed-order reductions (bitwise reproducible), every spin bounded.
+// The persistent kernels keep the ownership, the hand-off and the workspace of the LSTM's (mtl_lstm.hip): workgroup w owns the hidden
+// units [8 w, 8 w + 8) for the whole sequence, its 24 rows of W_hh (rows g H + j) stay in registers, one grid-wide hand-off per
+// step, fixed-order reductions (bitwise reproducible), every spin bounded.  Shared with the LSTM through mtl_handoff.h: the hand-off,
+// the backward's row-split partial product, the width dispatch, the launch and the counter reset.
 #include "mtl_handoff.h"
+#include "mtl_rnn_cell.h"
 
 namespace {
 
@@ -26,8 +26,6 @@ struct GruP {
     float *dgx, *dgh;
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 // ------------------------------------------------------------------------------------------------------ one time step, element-wise
 __global__ __launch_bounds__(256) void gru_cell_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ gh,
                                                            const float* __restrict__ h_prev, float* __restrict__ acts,
@@ -37,30 +35,13 @@ __global__ __launch_bounds__(256) void gru_cell_fwd_kernel(const float* __restri
     if (e >= B * H) return;
     const int b = e / H, j = e - b * H;
     const long g3 = (long)b * 3 * H + j, a4 = (long)b * 4 * H + j;
-    const float r = sigmoidf_(gx[g3] + gh[g3]), z = sigmoidf_(gx[g3 + H] + gh[g3 + H]), q = gh[g3 + 2 * H];
-    const float n = tanhf(gx[g3 + 2 * H] + r * q);
-    const float hn = (1.f - z) * n + z * h_prev[e];
-    acts[a4] = r;
-    acts[a4 + H] = z;
-    acts[a4 + 2 * H] = n;
-    acts[a4 + 3 * H] = q;
-    h[e] = hn;
-    if (h_drop) h_drop[e] = mask ? (mask[e] ? hn * mscale : 0.f) : hn;
-}
-
-struct GruGrad {
-    float da_r, da_z, da_n, dq, carry;
-};
-// the cell's backward for one (batch row, unit): shared by the per-step kernel and the persistent one (same arithmetic, same order)
-__device__ __forceinline__ GruGrad gru_cell_grad(float dh, float r, float z, float n, float q, float hprev) {
-    const float dn = dh * (1.f - z), dz = dh * (hprev - n);
-    GruGrad g;
-    g.da_n = dn * (1.f - n * n);
-    g.dq = g.da_n * r;
-    g.da_r = g.da_n * q * r * (1.f - r);
-    g.da_z = dz * z * (1.f - z);
-    g.carry = dh * z;
-    return g;
+    const GruAct a = gru_cell_act(gx, gh, g3, H, h_prev + e);
+    acts[a4] = a.r;
+    acts[a4 + H] = a.z;
+    acts[a4 + 2 * H] = a.n;
+    acts[a4 + 3 * H] = a.q;
+    h[e] = a.h;
+    if (h_drop) h_drop[e] = dropped(a.h, mask, e, mscale);
 }
 
 __global__ __launch_bounds__(256) void gru_cell_bwd_kernel(const float* __restrict__ dh_up, const uint8_t* __restrict__ mask,
@@ -72,7 +53,7 @@ __global__ __launch_bounds__(256) void gru_cell_bwd_kernel(const float* __restri
     if (e >= B * H) return;
     const int b = e / H, j = e - b * H;
     const long g3 = (long)b * 3 * H + j, a4 = (long)b * 4 * H + j;
-    float dh = dh_up ? (mask ? (mask[e] ? dh_up[e] * mscale : 0.f) : dh_up[e]) : 0.f;
+    float dh = dh_up ? dropped(dh_up, mask, e, mscale) : 0.f;
     if (dh_rec) dh += dh_rec[e];
     if (carry_in) dh += carry_in[e];
     const GruGrad g = gru_cell_grad(dh, acts[a4], acts[a4 + H], acts[a4 + 2 * H], acts[a4 + 3 * H], h_prev[e]);
@@ -82,10 +63,9 @@ __global__ __launch_bounds__(256) void gru_cell_bwd_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------------- persistent forward
-constexpr int NCH = 16;                      // k chunks of the recurrent product
 // floats between the chunk planes of the partial-sum buffer [chunk][B][24 rows]: = 8 mod 64, so the 8 chunks x 8 units of a wave
 // write 64 different LDS banks
-__host__ __device__ inline int red_stride(int B) {
+__host__ __device__ constexpr int red_stride(int B) {
     const int rs = B * 24;
     return rs + (72 - rs % 64) % 64;
 }
@@ -93,6 +73,9 @@ __host__ __device__ inline int red_stride(int B) {
 // reads KH floats apart: the same banks for KH = 16 / 32) fall into different banks
 template <int KC>
 constexpr int state_stride() { return 8 * KC + 4 * NCH; }
+// dynamic LDS of gru_layer_fwd_kernel: the staged state [B][state_stride] + the chunk partials [NCH][red_stride]
+template <int KC>
+constexpr int gru_fwd_lds(int B) { return (B * state_stride<KC>() + NCH * red_stride(B)) * 4; }
 
 // B x H floats written by other workgroups -> LDS in the padded layout, 256 threads.  16-byte `sc1` loads, eight in flight behind ONE
 // wait inside the same statement (early-clobber outputs: the compiler cannot touch the destinations before the data has landed);
@@ -202,15 +185,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
                 for (int c = 0; c < NCH; ++c) s += red[c * RS + cb * 24 + g * 8 + cu];
                 gh[g] = s + bias[g];
             }
-            const float r = sigmoidf_(gxv[0] + gh[0]), z = sigmoidf_(gxv[1] + gh[1]), q = gh[2];
-            const float n = tanhf(gxv[2] + r * q);
-            const float hn = (1.f - z) * n + z * h_prev;
+            const GruAct a = gru_cell_act(gxv, gh, 0, 1, &h_prev);
             float* ac = p.acts + row * 4 * H + cj;
-            ac[0] = r, ac[H] = z, ac[2 * H] = n, ac[3 * H] = q;
+            ac[0] = a.r, ac[H] = a.z, ac[2 * H] = a.n, ac[3 * H] = a.q;
             const long e = row * H + cj;
-            store_shared(p.hall + e + (long)B * H, hn);        // hall[t + 1]: read by every workgroup in the next step
-            if (p.xout) p.xout[e] = p.mask ? (p.mask[e] ? hn * p.mscale : 0.f) : hn;
-            h_prev = hn;
+            store_shared(p.hall + e + (long)B * H, a.h);       // hall[t + 1]: read by every workgroup in the next step
+            if (p.xout) p.xout[e] = dropped(a.h, p.mask, e, p.mscale);
+            h_prev = a.h;
         }
         if (t + 1 < T) grid_arrive(p.sync);      // (its barrier also orders this step's LDS reads before the next step's writes)
     }
@@ -219,8 +200,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 // ------------------------------------------------------------------------------------------------------------ persistent backward
 // Same ownership in reverse time, as lstm_layer_bwd_kernel: the recurrent gradient dh_rec_t = dgh_{t+1} . W_hh is split by ROWS --
 // workgroup w multiplies the 24 columns of dgh_{t+1} it has just produced (in LDS) with its 24 rows of W_hh for all H outputs
-// (thread: 1-2 output units, 24 x 1-2 weights in registers) and publishes that partial (B x H, write-through); after the hand-off
-// every workgroup sums the partials of its own 8 units over the workgroups in a fixed order.  Two partial buffers alternate with the
+// (rowsplit_partial, mtl_handoff.h) and publishes that partial (B x H, write-through); after the hand-off every workgroup sums the
+// partials of its own 8 units over the workgroups in a fixed order.  Two partial buffers alternate with the
 // step parity.  The direct carry dh' z stays in the owning thread's register: no hand-off.
 //
 // The sum over the N = H / 8 partials of one (batch row, unit): N `sc1` dword loads (uniform base of partial k in SGPRs + this lane's
@@ -269,14 +250,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     const int jt = tid * JT;                      // first output unit of this thread
     const bool active = jt < H;
     float w[24][JT];
-    if (active) {
-#pragma unroll
-        for (int r = 0; r < 24; ++r) {
-            const float* q = p.whh + (long)((r >> 3) * H + j0 + (r & 7)) * H + jt;
-#pragma unroll
-            for (int c = 0; c < JT; ++c) w[r][c] = q[c];
-        }
-    }
+    if (active) load_rowsplit_weights<8 * KC>(w, p.whh, jt);
     float* P = reinterpret_cast<float*>(p.sync) + HDR;        // two buffers of [nwg][B][H] behind the header
     const long pbuf = (long)nwg * B * H;
     const bool cell = tid < B * LU;
@@ -290,7 +264,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         if (cell) {
             const long row = (long)t * B + cb;
             const long e = row * H + cj;
-            dh_up = p.dx_up ? (p.mask ? (p.mask[e] ? p.dx_up[e] * p.mscale : 0.f) : p.dx_up[e]) : 0.f;
+            dh_up = p.dx_up ? dropped(p.dx_up, p.mask, e, p.mscale) : 0.f;
             const float* ac = p.acts + row * 4 * H + cj;
             ar = ac[0], az = ac[H], an = ac[2 * H], aq = ac[3 * H];
             hprev = p.hall[e];                                  // hall[t]: written by the forward launch
@@ -315,54 +289,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         }
         if (t > 0) {
             __syncthreads();
-            if (active) {
-                float* out = P + (t & 1) * pbuf + (long)blockIdx.x * B * H + jt;
-#pragma unroll 1
-                for (int b = 0; b < B; ++b) {
-                    const float* gb = dgs + b * 24;
-                    float a[JT];
-#pragma unroll
-                    for (int c = 0; c < JT; ++c) a[c] = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 24; r += 4) {
-                        const float4 gv = *reinterpret_cast<const float4*>(gb + r);
-#pragma unroll
-                        for (int c = 0; c < JT; ++c) {
-                            a[c] = fmaf(gv.x, w[r][c], a[c]);
-                            a[c] = fmaf(gv.y, w[r + 1][c], a[c]);
-                            a[c] = fmaf(gv.z, w[r + 2][c], a[c]);
-                            a[c] = fmaf(gv.w, w[r + 3][c], a[c]);
-                        }
-                    }
-                    if (JT == 2) {
-                        const unsigned long long u = (unsigned long long)__builtin_bit_cast(unsigned, a[0]) |
-                                                     ((unsigned long long)__builtin_bit_cast(unsigned, a[JT - 1]) << 32);
-                        __hip_atomic_store(reinterpret_cast<unsigned long long*>(out + (long)b * H), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-                        store_shared(out + (long)b * H, a[0]);
-                    }
-                }
-            }
+            if (active) rowsplit_partial(w, dgs, P + (t & 1) * pbuf + (long)blockIdx.x * B * H + jt, B, H);
             grid_arrive(p.sync);      // (its barrier also orders the reads of dgs before the next step's writes)
         }
     }
-}
-
-template <int KC>
-int launch_fwd(const GruP& p, hipStream_t s) {
-    const int smem = (p.B * state_stride<KC>() + NCH * red_stride(p.B)) * 4;
-    static int attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gru_layer_fwd_kernel<KC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (32 * state_stride<KC>() + NCH * red_stride(32)) * 4) == hipSuccess ? 0 : MTL_ELAUNCH;
-    if (attr) return attr;
-    hipLaunchKernelGGL(gru_layer_fwd_kernel<KC>, dim3(p.H / LU), dim3(256), smem, s, p);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
-}
-template <int KC>
-int launch_bwd(const GruP& p, hipStream_t s) {
-    hipLaunchKernelGGL(gru_layer_bwd_kernel<KC>, dim3(p.H / LU), dim3(256), p.B * 24 * 4, s, p);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
 }
 
 }  // namespace
@@ -394,29 +324,21 @@ int mtl_gru_layer_fwd(void* stream, const float* gx, const float* w_hh, const fl
                       const unsigned char* mask, float mscale, int T, int B, int H, void* workspace) {
     if (!gx || !w_hh || !b_hh || !hall || !acts || !workspace || T <= 0 || !mtl_gru_layer_supported(B, H)) return MTL_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(workspace, 0, 4, s) != hipSuccess) return MTL_ELAUNCH;      // the arrival counter; the error word [1] is sticky
+    if (const int rc = reset_counter(workspace, s)) return rc;
     GruP p{gx, w_hh, b_hh, hall, acts, xout, mask, mscale, T, B, H, reinterpret_cast<unsigned*>(workspace), nullptr, nullptr, nullptr};
-    switch (H / 8) {
-        case 16: return launch_fwd<16>(p, s);
-        case 32: return launch_fwd<32>(p, s);
-        case 48: return launch_fwd<48>(p, s);
-        default: return launch_fwd<64>(p, s);
-    }
+    return dispatch_kc(H, [&](auto kc) {
+        return launch_persistent<gru_layer_fwd_kernel<kc()>>(H / LU, gru_fwd_lds<kc()>(B), gru_fwd_lds<kc()>(MAXB), s, p);
+    });
 }
 
 int mtl_gru_layer_bwd(void* stream, const float* dx_up, const unsigned char* mask, float mscale, const float* w_hh, const float* acts,
                       const float* hall, float* dgx, float* dgh, int T, int B, int H, void* workspace) {
     if (!w_hh || !acts || !hall || !dgx || !dgh || !workspace || T <= 0 || !mtl_gru_layer_supported(B, H)) return MTL_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(workspace, 0, 4, s) != hipSuccess) return MTL_ELAUNCH;      // the arrival counter; the error word [1] is sticky
+    if (const int rc = reset_counter(workspace, s)) return rc;
     GruP p{nullptr, w_hh, nullptr, const_cast<float*>(hall), const_cast<float*>(acts), nullptr, mask, mscale, T, B, H,
            reinterpret_cast<unsigned*>(workspace), dx_up, dgx, dgh};
-    switch (H / 8) {
-        case 16: return launch_bwd<16>(p, s);
-        case 32: return launch_bwd<32>(p, s);
-        case 48: return launch_bwd<48>(p, s);
-        default: return launch_bwd<64>(p, s);
-    }
+    return dispatch_kc(H, [&](auto kc) { return launch_persistent<gru_layer_bwd_kernel<kc()>>(H / LU, B * 24 * 4, 0, s, p); });
 }
 
 }  // extern "C"

@@ -7,15 +7,18 @@
 //     holds W_hh[row r][kc H/8 .. + H/8) (<= 64 registers);
 //   * per step the previous hidden state (B x H, <= 64 KB) is staged in LDS and every thread multiplies its row chunk with the
 //     B batch rows (operand reads are LDS broadcasts), the 8 chunk partials of an output are summed in a fixed order, the
-//     threads (b, unit) apply the cell (same formulas as lstm_cell_fwd_kernel, mtl_elem.hip) and store h_t, c_t, the gate
-//     activations and the (dropped) copy for the next layer;
+//     threads (b, unit) apply the cell (lstm_cell_act, mtl_rnn_cell.h: the per-step lstm_cell_fwd_kernel below calls the same) and
+//     store h_t, c_t, the gate activations and the (dropped) copy for the next layer;
 //   * a grid-wide hand-off per step: write-through (sc1) stores of the shared payload -> vmcnt(0) -> workgroup barrier -> one lane
 //     arrives on a monotonic counter; consumers: one lane polls (relaxed, agent scope), workgroup barrier, sc1 loads.  Every spin
 //     is bounded (an error word is set instead of hanging the device); the grid is H / 8 <= 64 workgroups, far below the 256 CUs,
 //     so all of them are resident.
 // The backward runs the same ownership in reverse time (see lstm_layer_bwd_kernel).  The weight gradients remain three products
 // over all T steps (lm.py).  Reductions are fixed-order: bitwise reproducible.
-#include "mtl_handoff.h"      // LU, SPIN_LIMIT, HDR, PBUF, grid_wait / grid_arrive / store_shared (shared with mtl_gru.hip)
+// Shared with mtl_gru.hip: the cell arithmetic and the dropout convention (mtl_rnn_cell.h); the workspace layout, the hand-off, the
+// layer backward's row-split partial product, the width dispatch, the launch and the header resets (mtl_handoff.h).
+#include "mtl_handoff.h"
+#include "mtl_rnn_cell.h"
 
 namespace {
 
@@ -33,7 +36,50 @@ struct LstmP {
     float* dG;
 };
 
-// (the hand-off itself -- grid_wait / grid_arrive / store_shared -- is in mtl_handoff.h)
+// ------------------------------------------------------------------ LSTM cell (lm/model/rnn_model.py:20 nn.LSTM), one time step
+// gates = gx + gh (both B x 4H, biases already added by the two GEMMs), torch order [i | f | g | o]; acts = the activated gates,
+// c, h and the optional dropped copy of h for the next layer
+__global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ gh,
+                                                            const float* __restrict__ c_prev, float* __restrict__ acts,
+                                                            float* __restrict__ c, float* __restrict__ h, float* __restrict__ h_drop,
+                                                            const uint8_t* __restrict__ mask, float mscale, int B, int H) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= B * H) return;
+    const int b = e / H, j = e - b * H;
+    const long base = (long)b * 4 * H + j;
+    const float pre[4] = {gx[base] + gh[base], gx[base + H] + gh[base + H], gx[base + 2 * H] + gh[base + 2 * H],
+                          gx[base + 3 * H] + gh[base + 3 * H]};
+    const LstmAct a = lstm_cell_act(pre, c_prev[e]);
+    acts[base] = a.i;
+    acts[base + H] = a.f;
+    acts[base + 2 * H] = a.g;
+    acts[base + 3 * H] = a.o;
+    c[e] = a.c;
+    h[e] = a.h;
+    if (h_drop) h_drop[e] = dropped(a.h, mask, e, mscale);
+}
+// dh = dh_up [* mask * mscale] + dh_rec (both nullable), dc_next nullable: dgates = the pre-activation gradients, dc_prev = dc f
+__global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restrict__ dh_up, const uint8_t* __restrict__ mask,
+                                                            float mscale, const float* __restrict__ dh_rec,
+                                                            const float* __restrict__ dc_next, const float* __restrict__ acts,
+                                                            const float* __restrict__ c, const float* __restrict__ c_prev,
+                                                            float* __restrict__ dgates, float* __restrict__ dc_prev, int B, int H) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= B * H) return;
+    const int b = e / H, j = e - b * H;
+    const long base = (long)b * 4 * H + j;
+    float dh = dh_up ? dropped(dh_up, mask, e, mscale) : 0.f;
+    if (dh_rec) dh += dh_rec[e];
+    const LstmGrad d = lstm_cell_grad(dh, dc_next, e, acts[base], acts[base + H], acts[base + 2 * H], acts[base + 3 * H],
+                                      c[e], c_prev + e);
+    dgates[base] = d.di;
+    dgates[base + H] = d.df;
+    dgates[base + 2 * H] = d.dg;
+    dgates[base + 3 * H] = d.do_;
+    dc_prev[e] = d.dc_prev;
+}
+
+// ------------------------------------------------------------------------------------------------------------- persistent layer
 // B x H floats written by other workgroups -> LDS (same linear layout), 256 threads.  16-byte `sc1` loads issued back to back with ONE
 // wait: the relaxed agent-scope atomic loads of HIP (`__hip_atomic_load`) are kept in program order by the compiler -- a wait after every
 // load -- which made this copy a chain of 20 memory round trips (5.0 us of a 13.6 us step, measured with s_memrealtime stamps;
@@ -135,20 +181,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             for (int g = 0; g < 4; ++g) {
                 float s = 0.f;
 #pragma unroll
-                for (int q = 0; q < 16; ++q) s += red[(q * B + cb) * 32 + g * 8 + cu];
+                for (int q = 0; q < NCH; ++q) s += red[(q * B + cb) * 32 + g * 8 + cu];
                 pre[g] = gxv[g] + (s + bias[g]);
             }
-            const float ai = 1.f / (1.f + expf(-pre[0])), af = 1.f / (1.f + expf(-pre[1])), ag = tanhf(pre[2]),
-                        ao = 1.f / (1.f + expf(-pre[3]));
-            const float cn = af * c_prev + ai * ag;
-            const float hn = ao * tanhf(cn);
+            const LstmAct a = lstm_cell_act(pre, c_prev);
             float* ac = p.acts + row * 4 * H + cj;
-            ac[0] = ai, ac[H] = af, ac[2 * H] = ag, ac[3 * H] = ao;
+            ac[0] = a.i, ac[H] = a.f, ac[2 * H] = a.g, ac[3 * H] = a.o;
             const long e = row * H + cj;
-            p.call[e + (long)B * H] = cn;              // call[t + 1]
-            store_shared(p.hall + e + (long)B * H, hn);        // hall[t + 1]: read by every workgroup in the next step
-            if (p.xout) p.xout[e] = p.mask ? (p.mask[e] ? hn * p.mscale : 0.f) : hn;
-            c_prev = cn;
+            p.call[e + (long)B * H] = a.c;             // call[t + 1]
+            store_shared(p.hall + e + (long)B * H, a.h);       // hall[t + 1]: read by every workgroup in the next step
+            if (p.xout) p.xout[e] = dropped(a.h, p.mask, e, p.mscale);
+            c_prev = a.c;
         }
         if (t + 1 < T) grid_arrive(p.sync);
     }
@@ -173,14 +216,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     const int jt = tid * JT;                      // first output unit of this thread
     const bool active = jt < H;
     float w[32][JT];
-    if (active) {
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const float* q = p.whh + (long)((r >> 3) * H + j0 + (r & 7)) * H + jt;
-#pragma unroll
-            for (int c = 0; c < JT; ++c) w[r][c] = q[c];
-        }
-    }
+    if (active) load_rowsplit_weights<8 * KC>(w, p.whh, jt);
     float* P = reinterpret_cast<float*>(p.sync) + HDR;        // two buffers of [nwg][B][H] behind the header
     const long pbuf = (long)nwg * B * H;
     const bool cell = tid < B * LU;
@@ -194,7 +230,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         if (cell) {
             const long row = (long)t * B + cb;
             const long e = row * H + cj;
-            dh_up = p.dx_up ? (p.mask ? (p.mask[e] ? p.dx_up[e] * p.mscale : 0.f) : p.dx_up[e]) : 0.f;
+            dh_up = p.dx_up ? dropped(p.dx_up, p.mask, e, p.mscale) : 0.f;
             const float* ac = p.acts + row * 4 * H + cj;
             ai = ac[0], af = ac[H], ag = ac[2 * H], ao = ac[3 * H];
             cc = p.call[e + (long)B * H], cprev = p.call[e];
@@ -214,47 +250,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         }
         if (cell) {
             const long row = (long)t * B + cb;
-            const float dh = dh_up + dh_rec;
-            const float tc = tanhf(cc);
-            const float dc = dc_next + dh * ao * (1.f - tc * tc);
-            const float di = dc * ag * ai * (1.f - ai), df = dc * cprev * af * (1.f - af), dg_ = dc * ai * (1.f - ag * ag),
-                        do_ = dh * tc * ao * (1.f - ao);
+            const LstmGrad d = lstm_cell_grad(dh_up + dh_rec, &dc_next, 0, ai, af, ag, ao, cc, &cprev);
             float* dg = p.dG + row * 4 * H + cj;
-            dg[0] = di, dg[H] = df, dg[2 * H] = dg_, dg[3 * H] = do_;
+            dg[0] = d.di, dg[H] = d.df, dg[2 * H] = d.dg, dg[3 * H] = d.do_;
             float* l = dgs + cb * 32 + cu;
-            l[0] = di, l[8] = df, l[16] = dg_, l[24] = do_;
-            dc_next = dc * af;
+            l[0] = d.di, l[8] = d.df, l[16] = d.dg, l[24] = d.do_;
+            dc_next = d.dc_prev;
         }
         if (t > 0) {
             __syncthreads();
-            if (active) {
-                float* out = P + (t & 1) * pbuf + (long)blockIdx.x * B * H + jt;
-#pragma unroll 1
-                for (int b = 0; b < B; ++b) {
-                    const float* gb = dgs + b * 32;
-                    float a[JT];
-#pragma unroll
-                    for (int c = 0; c < JT; ++c) a[c] = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 32; r += 4) {
-                        const float4 gv = *reinterpret_cast<const float4*>(gb + r);
-#pragma unroll
-                        for (int c = 0; c < JT; ++c) {
-                            a[c] = fmaf(gv.x, w[r][c], a[c]);
-                            a[c] = fmaf(gv.y, w[r + 1][c], a[c]);
-                            a[c] = fmaf(gv.z, w[r + 2][c], a[c]);
-                            a[c] = fmaf(gv.w, w[r + 3][c], a[c]);
-                        }
-                    }
-                    if (JT == 2) {
-                        const unsigned long long u = (unsigned long long)__builtin_bit_cast(unsigned, a[0]) |
-                                                     ((unsigned long long)__builtin_bit_cast(unsigned, a[JT - 1]) << 32);
-                        __hip_atomic_store(reinterpret_cast<unsigned long long*>(out + (long)b * H), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-                        store_shared(out + (long)b * H, a[0]);
-                    }
-                }
-            }
+            if (active) rowsplit_partial(w, dgs, P + (t & 1) * pbuf + (long)blockIdx.x * B * H + jt, B, H);
             grid_arrive(p.sync);
         }
     }
@@ -388,7 +393,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
                 for (int g = 0; g < 4; ++g) {
                     float s = 0.f;
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) s += red[(q * B + cb) * 32 + g * 8 + cu];
+                    for (int q = 0; q < NCH; ++q) s += red[(q * B + cb) * 32 + g * 8 + cu];
                     store_shared(gx + ((long)t * B + cb) * 4 * H + g * H + cj, s + bias[g]);
                 }
             }
@@ -428,20 +433,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             for (int g = 0; g < 4; ++g) {
                 float s = 0.f;
 #pragma unroll
-                for (int q = 0; q < 16; ++q) s += red[(q * B + cb) * 32 + g * 8 + cu];
+                for (int q = 0; q < NCH; ++q) s += red[(q * B + cb) * 32 + g * 8 + cu];
                 pre[g] = gxv[g] + (s + bias[g]);
             }
-            const float ai = 1.f / (1.f + expf(-pre[0])), af = 1.f / (1.f + expf(-pre[1])), ag = tanhf(pre[2]),
-                        ao = 1.f / (1.f + expf(-pre[3]));
-            const float cn = af * c_prev + ai * ag;
-            const float hn = ao * tanhf(cn);
+            const LstmAct a = lstm_cell_act(pre, c_prev);
             float* ac = acts + row * 4 * H + cj;
-            ac[0] = ai, ac[H] = af, ac[2 * H] = ag, ac[3 * H] = ao;
+            ac[0] = a.i, ac[H] = a.f, ac[2 * H] = a.g, ac[3 * H] = a.o;
             const long e = row * H + cj;
-            call[e + (long)B * H] = cn;
-            store_shared(hall + e + (long)B * H, hn);
-            store_shared(xout + e, mask ? (mask[e] ? hn * p.mscale : 0.f) : hn);      // read by the group above
-            c_prev = cn;
+            call[e + (long)B * H] = a.c;
+            store_shared(hall + e + (long)B * H, a.h);
+            store_shared(xout + e, dropped(a.h, mask, e, p.mscale));      // read by the group above
+            c_prev = a.c;
         }
         flags_arrive(own + wg, (unsigned)(t + 1));      // also after the last step: the group above waits for it
         if (l > 0 && t + 1 < T) fetch_gx(t + 1);
@@ -559,15 +561,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (cell) {
             const long row = (long)t * B + cb;
             const float dh = dh_up + dh_rec;
-            const float tc = tanhf(cc);
-            const float dc = dc_next + dh * ao * (1.f - tc * tc);
-            const float di = dc * ag * ai * (1.f - ai), df = dc * cprev * af * (1.f - af), dg_ = dc * ai * (1.f - ag * ag),
-                        do_ = dh * tc * ao * (1.f - ao);
+            const LstmGrad d = lstm_cell_grad(dh, &dc_next, 0, ai, af, ag, ao, cc, &cprev);
             float* dg = dG + row * 4 * H + cj;
-            dg[0] = di, dg[H] = df, dg[2 * H] = dg_, dg[3 * H] = do_;
+            dg[0] = d.di, dg[H] = d.df, dg[2 * H] = d.dg, dg[3 * H] = d.do_;
             float* q = dgs + cb * 32 + cu;
-            q[0] = di, q[8] = df, q[16] = dg_, q[24] = do_;
-            dc_next = dc * af;
+            q[0] = d.di, q[8] = d.df, q[16] = d.dg, q[24] = d.do_;
+            dc_next = d.dc_prev;
         }
         __syncthreads();
         if (t > 0) {
@@ -580,40 +579,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (l > 0) flags_arrive(own + wg, (unsigned)T);
 }
 
-template <int KC>
-int launch_fwd(const LstmP& p, hipStream_t s) {
-    const int smem = (p.B * 8 * KC + 16 * p.B * 32) * 4;
-    static int attr = hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_layer_fwd_kernel<KC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (32 * 8 * KC + 16 * 32 * 32) * 4) == hipSuccess ? 0 : MTL_ELAUNCH;
-    if (attr) return attr;
-    hipLaunchKernelGGL(lstm_layer_fwd_kernel<KC>, dim3(p.H / LU), dim3(256), smem, s, p);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
-}
-template <int KC>
-int launch_bwd(const LstmP& p, hipStream_t s) {
-    const int smem = p.B * 32 * 4;
-    hipLaunchKernelGGL(lstm_layer_bwd_kernel<KC>, dim3(p.H / LU), dim3(256), smem, s, p);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
-}
-
-template <int KC>
-int launch_stack_fwd(const StackP& p, hipStream_t s) {
-    const int smem = (p.B * 8 * KC + 16 * p.B * 32) * 4;
-    static int attr = hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_stack_fwd_kernel<KC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (32 * 8 * KC + 16 * 32 * 32) * 4) == hipSuccess ? 0 : MTL_ELAUNCH;
-    if (attr) return attr;
-    hipLaunchKernelGGL(lstm_stack_fwd_kernel<KC>, dim3((2 * p.NL - 1) * (p.H / LU)), dim3(256), smem, s, p);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
-}
-template <int KC>
-int launch_stack_bwd(const StackP& p, hipStream_t s) {
-    hipLaunchKernelGGL(lstm_stack_bwd_kernel<KC>, dim3(p.NL * (p.H / LU)), dim3(256), p.B * 32 * 4, s, p);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
-}
+// dynamic LDS of lstm_layer_fwd_kernel and lstm_stack_fwd_kernel (one layout): the staged operand [B][H] + the chunk partials
+// [NCH][B][32 rows]; the backward kernels hold dG_t [B][32]
+constexpr int lstm_fwd_lds(int B, int H) { return (B * H + NCH * B * 32) * 4; }
+constexpr int lstm_bwd_lds(int B) { return B * 32 * 4; }
 
 bool fill_stack(StackP& p, const mtl_lstm_stack* d, int NL, bool bwd) {
     for (int l = 0; l < NL; ++l) {
@@ -639,8 +608,27 @@ static int lstm_resident_limit() {
         n = 256;                          // no device visible (shape queries on a build host): the MI355X's own count
     return n - n / 8;
 }
+int mtl_lstm_cell_fwd(void* stream, const float* gx, const float* gh, const float* c_prev, float* acts, float* c, float* h,
+                      float* h_drop, const unsigned char* mask, float mscale, int B, int H) {
+    if (!gx || !gh || !c_prev || !acts || !c || !h || B <= 0 || H <= 0) return MTL_EINVAL;
+    hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3((B * H + 255) / 256), dim3(256), 0, as_stream(stream), gx, gh, c_prev, acts, c, h,
+                       h_drop, mask, mscale, B, H);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
+
+int mtl_lstm_cell_bwd(void* stream, const float* dh_up, const unsigned char* mask, float mscale, const float* dh_rec,
+                      const float* dc_next, const float* acts, const float* c, const float* c_prev, float* dgates, float* dc_prev,
+                      int B, int H) {
+    if (!acts || !c || !c_prev || !dgates || !dc_prev || B <= 0 || H <= 0) return MTL_EINVAL;
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3((B * H + 255) / 256), dim3(256), 0, as_stream(stream), dh_up, mask, mscale, dh_rec,
+                       dc_next, acts, c, c_prev, dgates, dc_prev, B, H);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
+
 int mtl_lstm_layer_supported(int B, int H) {
-    return B >= 1 && B <= 32 && (H == 128 || H == 256 || H == 384 || H == 512) && H / LU <= lstm_resident_limit();
+    return B >= 1 && B <= MAXB && (H == 128 || H == 256 || H == 384 || H == 512) && H / LU <= lstm_resident_limit();
 }
 
 long mtl_lstm_layer_workspace(void) { return HDR * 4 + MAXL * 2 * PBUF * 4; }      // header + two partial buffers per layer (backward)
@@ -657,13 +645,10 @@ int mtl_lstm_stack_fwd(void* stream, const mtl_lstm_stack* layers, float mscale,
     if (!fill_stack(p, layers, NL, false)) return MTL_EINVAL;
     p.mscale = mscale, p.T = T, p.B = B, p.H = H, p.NL = NL, p.sync = reinterpret_cast<unsigned*>(workspace);
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(static_cast<char*>(workspace) + 256, 0, (HDR - 64) * 4, s) != hipSuccess) return MTL_ELAUNCH;      // the step flags; the error word [1] is sticky
-    switch (H / 8) {
-        case 16: return launch_stack_fwd<16>(p, s);
-        case 32: return launch_stack_fwd<32>(p, s);
-        case 48: return launch_stack_fwd<48>(p, s);
-        default: return launch_stack_fwd<64>(p, s);
-    }
+    if (const int rc = reset_flags(workspace, s)) return rc;
+    return dispatch_kc(H, [&](auto kc) {
+        return launch_persistent<lstm_stack_fwd_kernel<kc()>>((2 * NL - 1) * (H / LU), lstm_fwd_lds(B, H), lstm_fwd_lds(MAXB, H), s, p);
+    });
 }
 
 int mtl_lstm_stack_bwd(void* stream, const mtl_lstm_stack* layers, const float* dx_up, float mscale, float* scratch, int T, int B, int H,
@@ -673,42 +658,29 @@ int mtl_lstm_stack_bwd(void* stream, const mtl_lstm_stack* layers, const float* 
     if (!fill_stack(p, layers, NL, true)) return MTL_EINVAL;
     p.dx_up = dx_up, p.p2 = scratch, p.mscale = mscale, p.T = T, p.B = B, p.H = H, p.NL = NL, p.sync = reinterpret_cast<unsigned*>(workspace);
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(static_cast<char*>(workspace) + 256, 0, (HDR - 64) * 4, s) != hipSuccess) return MTL_ELAUNCH;      // the step flags; the error word [1] is sticky
-    switch (H / 8) {
-        case 16: return launch_stack_bwd<16>(p, s);
-        case 32: return launch_stack_bwd<32>(p, s);
-        case 48: return launch_stack_bwd<48>(p, s);
-        default: return launch_stack_bwd<64>(p, s);
-    }
+    if (const int rc = reset_flags(workspace, s)) return rc;
+    return dispatch_kc(H, [&](auto kc) { return launch_persistent<lstm_stack_bwd_kernel<kc()>>(NL * (H / LU), lstm_bwd_lds(B), 0, s, p); });
 }
 
 int mtl_lstm_layer_fwd(void* stream, const float* gx, const float* w_hh, const float* b_hh, float* hall, float* call, float* acts,
                        float* xout, const unsigned char* mask, float mscale, int T, int B, int H, void* workspace) {
     if (!gx || !w_hh || !b_hh || !hall || !call || !acts || !workspace || T <= 0 || !mtl_lstm_layer_supported(B, H)) return MTL_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(workspace, 0, 4, s) != hipSuccess) return MTL_ELAUNCH;      // the arrival counter; the error word [1] is sticky
+    if (const int rc = reset_counter(workspace, s)) return rc;
     LstmP p{gx, w_hh, b_hh, hall, call, acts, xout, mask, mscale, T, B, H, reinterpret_cast<unsigned*>(workspace), nullptr, nullptr};
-    switch (H / 8) {
-        case 16: return launch_fwd<16>(p, s);
-        case 32: return launch_fwd<32>(p, s);
-        case 48: return launch_fwd<48>(p, s);
-        default: return launch_fwd<64>(p, s);
-    }
+    return dispatch_kc(H, [&](auto kc) {
+        return launch_persistent<lstm_layer_fwd_kernel<kc()>>(H / LU, lstm_fwd_lds(B, H), lstm_fwd_lds(MAXB, H), s, p);
+    });
 }
 
 int mtl_lstm_layer_bwd(void* stream, const float* dx_up, const unsigned char* mask, float mscale, const float* w_hh, const float* acts,
                        const float* call, float* dG, int T, int B, int H, void* workspace) {
     if (!w_hh || !acts || !call || !dG || !workspace || T <= 0 || !mtl_lstm_layer_supported(B, H)) return MTL_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(workspace, 0, 4, s) != hipSuccess) return MTL_ELAUNCH;      // the arrival counter; the error word [1] is sticky
+    if (const int rc = reset_counter(workspace, s)) return rc;
     LstmP p{nullptr, w_hh, nullptr, nullptr, const_cast<float*>(call), const_cast<float*>(acts), nullptr, mask, mscale, T, B, H,
             reinterpret_cast<unsigned*>(workspace), dx_up, dG};
-    switch (H / 8) {
-        case 16: return launch_bwd<16>(p, s);
-        case 32: return launch_bwd<32>(p, s);
-        case 48: return launch_bwd<48>(p, s);
-        default: return launch_bwd<64>(p, s);
-    }
+    return dispatch_kc(H, [&](auto kc) { return launch_persistent<lstm_layer_bwd_kernel<kc()>>(H / LU, lstm_bwd_lds(B), 0, s, p); });
 }
 
 }  // extern "C"

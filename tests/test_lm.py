@@ -266,3 +266,69 @@ def test_lm_persistent_lstm_layer_kernels(H, B, T, dropout, NL, E):
     with pytest.raises(RuntimeError, match='timed out'):
         eng.check_handoff()
     eng.check_handoff()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('B,H', [(1, 8), (3, 200), (32, 512)])
+@pytest.mark.parametrize('masked', [False, True])
+def test_lstm_cell_kernels(B, H, masked):
+    """mtl_lstm_cell_fwd / mtl_lstm_cell_bwd alone (the per-step path's cell, csrc/mtl_lstm.hip) against a restatement in fp64, with
+    and without the keep-mask, the backward from the device's own saved activations and cell state, with and without the recurrent
+    terms (dh_rec, dc_next: the last step has neither).  As for tests/test_lm_gru_gpu.py::test_gru_cell_kernels every output is a
+    sum / product of at most eight fp32 operations (each within an ulp, 6e-8 relative; expf / tanhf a few ulp) on the given inputs:
+    the bound is 1e-6 -- more than ten ulp -- times the largest magnitude a result can take: max(1, |c_prev|) forward (|c| <=
+    |c_prev| + 1, every gate within [-1, 1]), max(1, |dh| + |dc_next|) times that backward (dc <= |dc_next| + |dh|, a gate
+    gradient is dc or dh times factors bounded by max(1, |c_prev|)).  Measured: at most 4.6e-7, profiles/lm_gru/errors.txt."""
+    import mtl_amd
+    lib, check = mtl_amd._lib.lib(), mtl_amd._lib.check
+    st = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(100 * B + H)
+    gx, gh, cp = torch.randn(B, 4 * H, generator=g), torch.randn(B, 4 * H, generator=g), torch.randn(B, H, generator=g)
+    keep = (torch.rand(B, H, generator=g) > 0.3).to(torch.uint8)
+    msc = 1.0 / 0.7 if masked else 1.0
+    d = lambda t: t.cuda().contiguous()
+    gx_d, gh_d, cp_d, keep_d = d(gx), d(gh), d(cp), d(keep)
+    mp = keep_d.data_ptr() if masked else None
+    acts, c, h, hd = (torch.empty(B, n, device='cuda') for n in (4 * H, H, H, H))
+    check(lib.mtl_lstm_cell_fwd(st, gx_d.data_ptr(), gh_d.data_ptr(), cp_d.data_ptr(), acts.data_ptr(), c.data_ptr(), h.data_ptr(), hd.data_ptr(),
+                                mp, msc, B, H), 'lstm_cell_fwd')
+    pi, pf, pg, po = (gx.double() + gh.double()).view(B, 4, H).unbind(1)
+    w_i, w_f, w_g, w_o = torch.sigmoid(pi), torch.sigmoid(pf), torch.tanh(pg), torch.sigmoid(po)
+    w_c = w_f * cp.double() + w_i * w_g
+    w_h = w_o * torch.tanh(w_c)
+    w_hd = w_h * keep.double() * msc if masked else w_h
+    tol = 1e-6 * max(1.0, float(cp.abs().max()))
+    e_f = max(float((acts.cpu().double() - torch.cat([w_i, w_f, w_g, w_o], 1)).abs().max()), float((c.cpu().double() - w_c).abs().max()),
+              float((h.cpu().double() - w_h).abs().max()), float((hd.cpu().double() - w_hd).abs().max()))
+    print('lm_lstm cell error B=%d H=%d masked=%d: forward %.3e (bound %.3e)' % (B, H, masked, e_f, tol))
+    assert e_f < tol
+    # h_drop is optional
+    h2 = torch.empty_like(h)
+    check(lib.mtl_lstm_cell_fwd(st, gx_d.data_ptr(), gh_d.data_ptr(), cp_d.data_ptr(), acts.data_ptr(), c.data_ptr(), h2.data_ptr(), None, mp,
+                                msc, B, H), 'lstm_cell_fwd')
+    assert torch.equal(h, h2)
+    # backward from the device's own saved activations and cell state (identical inputs on both sides)
+    a_i, a_f, a_g, a_o = acts.cpu().double().view(B, 4, H).unbind(1)
+    tc = torch.tanh(c.cpu().double())
+    up, rec, dcn = torch.randn(B, H, generator=g), torch.randn(B, H, generator=g), torch.randn(B, H, generator=g)
+    up_d, rec_d, dcn_d = d(up), d(rec), d(dcn)
+    for last in (False, True):
+        dgates, dcp = torch.empty(B, 4 * H, device='cuda'), torch.empty(B, H, device='cuda')
+        check(lib.mtl_lstm_cell_bwd(st, up_d.data_ptr(), mp, msc, None if last else rec_d.data_ptr(), None if last else dcn_d.data_ptr(),
+                                    acts.data_ptr(), c.data_ptr(), cp_d.data_ptr(), dgates.data_ptr(), dcp.data_ptr(), B, H), 'lstm_cell_bwd')
+        dh = up.double() * (keep.double() * msc if masked else 1.0)
+        dc_in = torch.zeros(B, H, dtype=torch.float64)
+        if not last:
+            dh, dc_in = dh + rec.double(), dcn.double()
+        dc = dc_in + dh * a_o * (1 - tc * tc)
+        w_dg = torch.cat([dc * a_g * a_i * (1 - a_i), dc * cp.double() * a_f * (1 - a_f), dc * a_i * (1 - a_g * a_g), dh * tc * a_o * (1 - a_o)], 1)
+        tol_b = 1e-6 * max(1.0, float(dh.abs().max()) + float(dc_in.abs().max())) * max(1.0, float(cp.abs().max()))
+        e_b = max(float((dgates.cpu().double() - w_dg).abs().max()), float((dcp.cpu().double() - dc * a_f).abs().max()))
+        print('lm_lstm cell error B=%d H=%d masked=%d last=%d: backward %.3e (bound %.3e)' % (B, H, masked, last, e_b, tol_b))
+        assert e_b < tol_b
+    # bad arguments are refused before any launch
+    assert lib.mtl_lstm_cell_fwd(st, None, gh_d.data_ptr(), cp_d.data_ptr(), acts.data_ptr(), c.data_ptr(), h.data_ptr(), None, None, 1.0, B, H) == -22
+    assert lib.mtl_lstm_cell_bwd(st, up_d.data_ptr(), None, 1.0, None, None, acts.data_ptr(), c.data_ptr(), cp_d.data_ptr(), None, dcp.data_ptr(), B, H) == -22
+    assert lib.mtl_lstm_cell_fwd(st, gx_d.data_ptr(), gh_d.data_ptr(), cp_d.data_ptr(), acts.data_ptr(), c.data_ptr(), h.data_ptr(), None, None, 1.0, 0, H) == -22
+    assert lib.mtl_lstm_cell_bwd(st, up_d.data_ptr(), None, 1.0, None, None, acts.data_ptr(), c.data_ptr(), cp_d.data_ptr(), dgates.data_ptr(), dcp.data_ptr(), 0, H) == -22
+    torch.cuda.synchronize()
