@@ -661,6 +661,30 @@ int mtl_beam_rank(void* stream, const float* logits, const float* lse, int* stat
 int mtl_beam_gather(void* stream, float* const* caches_dev, int ncache, const int* parent, float* tmp, long tmp_floats, int rows, int t,
                     int width, long row_stride);
 
+/* ---- CTC loss (--loss ctc): utils/metrics.py:127-148 = F.ctc_loss(log_softmax(pred), gold, sizes, trg_lengths, 'mean') ------------
+ * U utterances of T rows each: logits (U T, ld) fp32, gold one row of ldg int64 per utterance of which the first tgt_len[u] entries
+ * are the labels, in_len / tgt_len (U) int32 ON THE DEVICE.  The kernels clamp in_len to [0, T] and tgt_len to [0, min(Lmax, ldg)];
+ * an utterance with a label outside [0, V) is infeasible.  The forward forms each row's log-sum-exp itself, as an fp32 pair hi + lo
+ * (mtl_ce_argmax_fwd's single-fp32 `lse` would put its rounding, 1e-6 at |logit| ~ 30, into every log-probability).
+ *   nll[u]      = -log p(labels_u | rows 0..in_len[u]-1), +inf when no alignment exists (also in_len = 0 with tgt_len > 0; 0 when both
+ *                 are 0), exactly reduction='none' with zero_infinity=False
+ *   loss_out[g] = sum over the per_group utterances of group g of nll_u / max(tgt_len_u, 1), / per_group   (U % per_group == 0; one
+ *                 loss per task, per_group = U is reduction='mean')
+ *   dlogits     = gscale * (gscale_dev ? gscale_dev[g] : 1) / (per_group max(tgt_len_u, 1)) * (softmax - label posterior) on the rows
+ *                 t < in_len[u] of a feasible utterance; exactly 0 on the other rows, on EVERY row of an infeasible utterance (torch's
+ *                 zero_infinity=True gradient; with False it writes NaN there) and in the columns V..ldd-1.  Every element of the
+ *                 (U T, ldd) rows is written.  Bitwise reproducible from run to run.
+ * ws (8-byte aligned): what the forward leaves for the backward -- the row statistics (U T) x 2 fp32 and the log-alpha lattice
+ * (U, T, 2 Lmax + 1) fp32 -- mtl_ctc_workspace bytes (-22 for U, T or Lmax outside 1.., Lmax > MTL_CTC_MAX_L).  Stream-ordered, no
+ * allocation, recordable. */
+#define MTL_CTC_MAX_L 1400
+long mtl_ctc_workspace(int U, int T, int Lmax);
+int mtl_ctc_fwd(void* stream, const float* logits, const long* gold, const int* in_len, const int* tgt_len, int U, int T, int V, int ld,
+                int ldg, int Lmax, int blank, int per_group, float* ws, long ws_bytes, float* nll, float* loss_out);
+int mtl_ctc_bwd(void* stream, const float* logits, const long* gold, const int* in_len, const int* tgt_len, int U, int T, int V, int ld,
+                int ldg, int Lmax, int blank, int per_group, const float* ws, long ws_bytes, const float* nll, float gscale,
+                const float* gscale_dev, float* dlogits, int ldd);
+
 /* ---- raw byte helpers on a stream (so that a whole task body consists of library calls only and can be replayed) ---- */
 int mtl_memset_zero(void* stream, void* dst, long bytes);
 int mtl_memcpy_d2d(void* stream, void* dst, const void* src, long bytes);

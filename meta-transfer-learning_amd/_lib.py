@@ -150,6 +150,9 @@ SIGNATURES = {
     'mtl_beam_state_words': (L, [I, I, I]),
     'mtl_beam_rank': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I]),
     'mtl_beam_gather': (I, [P, P, I, P, P, L, I, I, I, L]),
+    'mtl_ctc_workspace': (L, [I, I, I]),
+    'mtl_ctc_fwd': (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, L, P, P]),
+    'mtl_ctc_bwd': (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P, L, P, F, P, P, I]),
     'mtl_memset_zero': (I, [P, P, L]),
     'mtl_memcpy_d2d': (I, [P, P, P, L]),
     'mtl_event_record': (I, [P, P]),

@@ -95,6 +95,13 @@ def decoder_io(padded_target, pad_id=PAD_ID, sos_id=SOS_ID, eos_id=EOS_ID, width
     return torch.from_numpy(seq_in), torch.from_numpy(seq_out)
 
 
+def ctc_input_lengths(percentages, Td):
+    """utils/metrics.py:129 / transient_trainer.py:38: sizes = src_percentages.mul_(Td).int() -- an fp32 product, truncated (numpy in
+    fp32 reproduces it bit for bit; the caller's tensor is not scaled in place here)."""
+    return (np.asarray(percentages, dtype=np.float32) * np.float32(Td)).astype(np.int32)
+
+
+LOSS_TYPES = ('ce', 'ctc')
 _FULL = {'q': 'query', 'k': 'key', 'v': 'value'}
 
 
@@ -1092,13 +1099,15 @@ class PassEngine:
         self.flush_side()
 
     # ---------------------------------------------------------------- the pass
-    def prepare(self, lengths, target, B, T, slot=0, norm_count=None, width=None, frames=None):
+    def prepare(self, lengths, target, B, T, slot=0, norm_count=None, width=None, frames=None, percentages=None, target_sizes=None):
         """Host-side integer prep of one batch (modules/decoder.py:55-69 target shifting; every mask is derived inside the
         kernels from these few integers) + asynchronous H2D into STATIC per-slot buffers.  Kept separate from the kernels so
         a captured hipGraph of the pass can be replayed for any batch of the same shape."""
-        return self.prepare_tasks([(lengths, target)], B, T, slot, norm_count, width, frames=None if frames is None else [frames])
+        return self.prepare_tasks([(lengths, target)], B, T, slot, norm_count, width, frames=None if frames is None else [frames],
+                                  percentages=None if percentages is None else [percentages],
+                                  target_sizes=None if target_sizes is None else [target_sizes])
 
-    def prepare_tasks(self, batches, B, T, slot=0, norm_count=None, width=None, frames=None):
+    def prepare_tasks(self, batches, B, T, slot=0, norm_count=None, width=None, frames=None, percentages=None, target_sizes=None):
         """prepare() for the batches [(lengths, target)] of several tasks that one task-batched pass carries (all B samples x T
         frames; the decoder width is the largest of the tasks' -- positions beyond a task's own width are padding like any other:
         masked as keys, zeroed as rows, ignored by the loss).  Everything per-sample is concatenated in task order; the loss
@@ -1106,7 +1115,12 @@ class PassEngine:
         frames: the tasks' OWN frame counts when their batches were padded to different widths (data.py:77 pads a batch to its
         longest utterance) and stacked at the widest, T.  A task's encoder then has (frames // 2) // 2 positions as in its own
         pass: the positions beyond are padding (the reference compares RAW lengths with the positions it has, SURVEY Q2, so a wider
-        pad would otherwise turn into live positions), and forward_device clears the convolution outputs beyond each task's frames."""
+        pad would otherwise turn into live positions), and forward_device clears the convolution outputs beyond each task's frames.
+        percentages / target_sizes: per task, what the CTC loss stage (forward_device(loss_type='ctc')) takes its lengths from
+        (utils/metrics.py:129): in_len = (fp32 percentages * Td_own).int() with Td_own the task's OWN decoder width -- its longest
+        target + 1, as in its own reference pass, whatever width this pass is padded to -- and tgt_len = target_sizes.  None:
+        percentages = lengths / max(lengths) as data.py forms them, target_sizes = the count of non-PAD targets.  The two int32
+        arrays (nt * B each) stand at the END of the meta block."""
         hp = self.hp
         nt = len(batches)
         T4 = (T // 2) // 2
@@ -1125,11 +1139,24 @@ class PassEngine:
         pos = np.arange(T4)[None, :]
         dpos = np.arange(Td)[None, :]
         inv, klen_e, klen_d, keep_e, keep_d, firsts, nexts, n_nonpads = [], [], [], [], [], [], [], []
+        ctc_in, ctc_tg = [], []
+        for given in (percentages, target_sizes):
+            if given is not None and len(given) != nt:
+                raise ValueError('percentages / target_sizes: one entry per task')
+        host = lambda v: v.detach().to('cpu').numpy() if torch.is_tensor(v) else np.asarray(v)
         for ti, ((lengths, _target), (seq_in_t, seq_out_t)) in enumerate(zip(batches, ios)):
             seq_in, seq_out = seq_in_t.numpy(), seq_out_t.numpy()
             if seq_in.shape[0] != B:
                 raise ValueError('every task of a batched pass must bring %d samples' % B)
             lens = lengths.detach().to('cpu', torch.int64).numpy()
+            n_lab = (seq_out != PAD_ID).sum(1) - 1                  # labels per utterance (seq_out = labels, EOS, PAD...)
+            pct = host(percentages[ti]) if percentages is not None and percentages[ti] is not None else \
+                (lens / float(max(int(lens.max()), 1))).astype(np.float32)
+            sizes = host(target_sizes[ti]) if target_sizes is not None and target_sizes[ti] is not None else n_lab
+            if pct.shape != (B,) or sizes.shape != (B,):
+                raise ValueError('percentages / target_sizes: one value per sample')
+            ctc_in.append(ctc_input_lengths(pct, int(n_lab.max()) + 1))
+            ctc_tg.append(sizes.astype(np.int32))
             if frames is not None:
                 lens = np.minimum(lens, (frames[ti] // 2) // 2)     # a position the task's own pass does not have is padding
             is_pad = seq_in == EOS_ID
@@ -1166,7 +1193,7 @@ class PassEngine:
             torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).numpy().view(np.int32),   # dropout seed of this pass (torch CPU RNG), 8-byte aligned
             np.asarray(inv, dtype=np.float32).view(np.int32),                            # 1/n_nonpad (fp32 bits), per task
             np.zeros(head - 2 - nt, dtype=np.int32)] + klen_e + klen_d + keep_e + keep_d + firsts + nexts
-            + ([np.asarray(frames, dtype=np.int32)] if frames is not None else []))
+            + ([np.asarray(frames, dtype=np.int32)] if frames is not None else []) + ctc_in + ctc_tg)
         n_meta = int(meta_np.shape[0])
         seq_in = torch.cat([io[0] for io in ios]) if nt > 1 else ios[0][0]
         seq_out = torch.cat([io[1] for io in ios]) if nt > 1 else ios[0][1]
@@ -1215,13 +1242,16 @@ class PassEngine:
         embed_first = keep_dec + 4 * Bt * Td
         embed_next = embed_first + 4 * Bt * Td
         widths = embed_next + 4 * Bt * Td if frames is not None else None
-        return dict(frames=frames, widths=widths, seed=seed, B=B, T=T, Td=Td, nt=nt, n_nonpad=n_nonpads[0], n_nonpads=n_nonpads, gold_host=seq_out,
+        ctc_in_len = seed + 4 * (n_meta - 2 * Bt)
+        return dict(ctc_in_len=ctc_in_len, ctc_tgt_len=ctc_in_len + 4 * Bt, ctc_in_len_host=ctc_in, ctc_tgt_len_host=ctc_tg,
+frames=frames, widths=widths, seed=seed, B=B, T=T, Td=Td, nt=nt, n_nonpad=n_nonpads[0], n_nonpads=n_nonpads, gold_host=seq_out,
                     gold_hosts=[io[1] for io in ios], ids=ids, klen_enc=klen_enc, klen_dec=klen_dec,
                     keep_enc=keep_enc, keep_dec=keep_dec, embed_first=embed_first, embed_next=embed_next, inv_count=inv_count)
 
-    def forward(self, theta, x, lengths, target, smoothing=0.0, slot=0):
+    def forward(self, theta, x, lengths, target, smoothing=0.0, slot=0, loss_type='ce', percentages=None, target_sizes=None):
         """x (B,1,F,T) fp32 on device; lengths (B) int; target (B,L) int64 PAD-padded.  Returns a dict with device
-        tensors pred (B,Td,V), gold, hyp (B,Td) int64 and `loss` (1,) fp32; keeps what the backward needs."""
+        tensors pred (B,Td,V), gold, hyp (B,Td) int64 and `loss` (1,) fp32; keeps what the backward needs.
+        loss_type 'ctc': the CTC loss of prepare()'s percentages / target_sizes in place of the cross entropy (forward_device)."""
         if x.dim() != 4 or x.shape[1] != 1:
             raise ValueError('expected (B,1,F,T) input')
         # stand-alone passes (validation loops, the joint trainer, the drop-in autograd call) on batches whose width changes from call
@@ -1238,11 +1268,15 @@ class PassEngine:
                 xp.zero_()
                 xp[:, :, :, :T_own].copy_(x, non_blocking=True)
                 x, frames = xp, T_own
-        meta = self.prepare(lengths, target, x.shape[0], x.shape[3], slot, frames=frames)
-        return self.forward_device(theta, x, meta, smoothing)
+        meta = self.prepare(lengths, target, x.shape[0], x.shape[3], slot, frames=frames, percentages=percentages, target_sizes=target_sizes)
+        return self.forward_device(theta, x, meta, smoothing, loss_type=loss_type)
 
-    def forward_device(self, theta, x, meta, smoothing=0.0, hyp_out=None, loss_out=None, sP=0):
+    def forward_device(self, theta, x, meta, smoothing=0.0, hyp_out=None, loss_out=None, sP=0, loss_type='ce'):
         """Kernel launches only (hipGraph-capturable): everything batch-dependent comes from `meta`'s device buffers.
+
+        loss_type 'ctc' (utils/metrics.py:127-148): lse and hyp as for 'ce', then mtl_ctc_fwd writes one CTC loss per task into
+        `loss` from the lengths prepare() left at the end of the meta block; the log-alpha lattice stays in the arena for
+        backward(), which then forms d(logits) with mtl_ctc_bwd.  `smoothing` is ignored, as the reference ignores it.
 
         Task-batched pass (meta from prepare_tasks with nt > 1 tasks; trainer/asr/transient_trainer.py:178-237: the tasks of a
         meta-step are independent given theta0): x is (nt * B, 1, F, T) -- or (B, 1, F, T) when every task sees the SAME batch (the
@@ -1266,13 +1300,17 @@ class PassEngine:
         sX = B * F * T if Bx == nt * B and nt > 1 else 0          # task stride of the input (0: one batch shared by all tasks)
         if F // 2 // 2 * 128 != hp.d_in:
             raise ValueError('dim_input %d does not match %d frequency bins' % (hp.d_in, F))
+        if loss_type not in LOSS_TYPES:
+            raise NotImplementedError("loss_type must be 'ce' or 'ctc'")
+        if loss_type == 'ctc':
+            smoothing = 0.0
         self.nt, self.sP = nt, int(sP)
         try:
-            return self._forward_device(theta, x, meta, smoothing, hyp_out, loss_out, nt, sX, F, T)
+            return self._forward_device(theta, x, meta, smoothing, hyp_out, loss_out, nt, sX, F, T, loss_type)
         finally:
             self.nt, self.sP = 1, 0        # (the backward restores them from `saved`; an exception mid-pass must not leave nt > 1 behind)
 
-    def _forward_device(self, theta, x, meta, smoothing, hyp_out, loss_out, nt, sX, F, T):
+    def _forward_device(self, theta, x, meta, smoothing, hyp_out, loss_out, nt, sX, F, T, loss_type='ce'):
         hp, L, lib, st = self.hp, self.L, self.lib, self.stream
         sP = self.sP
         B = meta['B']
@@ -1353,8 +1391,20 @@ class PassEngine:
         else:
             check(lib.mtl_ce_argmax_fwd_g(st, pred.data_ptr(), gold_ptr, nt * Md, V, V, PAD_ID, float(smoothing), meta['inv_count'],
                                           lse.data_ptr(), hyp.data_ptr(), rowloss.data_ptr(), loss.data_ptr(), Md), 'ce_fwd')
+        ctc = None
+        if loss_type == 'ctc':
+            # one workgroup per utterance walks the (Td, 2 Lmax + 1) lattice of its labels (the first tgt_len entries of its gold
+            # row); the lattice and the rows' log-sum-exp pairs are kept for the backward, so they are a buffer of the pass and not the
+            # shared scratch (mtl_ctc_fwd forms its own row statistics: `lse` above is one fp32 per row, too coarse for x - lse near 0)
+            Lmax = max(Td - 1, 1)
+            ws_bytes = lib.mtl_ctc_workspace(Bt, Td, Lmax)
+            if ws_bytes < 0:
+                raise ValueError('ctc: %d decoder positions are beyond the kernels\' limit' % Td)
+            ctc = dict(Lmax=Lmax, ws_bytes=ws_bytes, ws=self.buf('ctc.lattice', (ws_bytes // 4,)), nll=self.buf('ctc.nll', (Bt,)))
+            check(lib.mtl_ctc_fwd(st, pred.data_ptr(), gold_ptr, meta['ctc_in_len'], meta['ctc_tgt_len'], Bt, Td, V, V, Td,
+                                  Lmax, PAD_ID, B, ctc['ws'].data_ptr(), ws_bytes, ctc['nll'].data_ptr(), loss.data_ptr()), 'ctc_fwd')
         self.saved = dict(S, Td=Td, n_nonpad=n_nonpad, smoothing=float(smoothing), klen_enc=klen_enc, klen_dec=klen_dec, keep_enc=keep_enc,
-                          keep_dec=keep_dec, dec_last=cur, enc_inputs=enc_inputs)
+                          keep_dec=keep_dec, dec_last=cur, enc_inputs=enc_inputs, loss_type=loss_type, ctc=ctc)
         if self.forward_hook is not None:
             self.forward_hook(self)
         # T4 / frames: the extent of the arena's encoder-side activations (a widened stand-alone pass, PassEngine.forward, carries
@@ -1650,8 +1700,14 @@ class PassEngine:
             ldd = (V + 3) // 4 * 4        # padded leading dimension -> 16-byte operand loads in the two GEMMs below
             dlog = self.buf('_dpred', (nt * Md, ldd))
             gold_ptr = S['meta']['ids'].data_ptr() + 8 * nt * Md
-            check(lib.mtl_ce_bwd_g(st, A['pred'].data_ptr(), A['lse'].data_ptr(), gold_ptr, nt * Md, V, V, PAD_ID, S['smoothing'],
-                                   float(scale), S['meta']['inv_count'], dlog.data_ptr(), ldd, Md), 'ce_bwd')
+            if S.get('loss_type', 'ce') == 'ctc':
+                C = S['ctc']
+                check(lib.mtl_ctc_bwd(st, A['pred'].data_ptr(), gold_ptr, S['meta']['ctc_in_len'],
+                                      S['meta']['ctc_tgt_len'], nt * B, Td, V, V, Td, C['Lmax'], PAD_ID, B, C['ws'].data_ptr(),
+                                      C['ws_bytes'], C['nll'].data_ptr(), float(scale), None, dlog.data_ptr(), ldd), 'ctc_bwd')
+            else:
+                check(lib.mtl_ce_bwd_g(st, A['pred'].data_ptr(), A['lse'].data_ptr(), gold_ptr, nt * Md, V, V, PAD_ID, S['smoothing'],
+                                       float(scale), S['meta']['inv_count'], dlog.data_ptr(), ldd, Md), 'ce_bwd')
             dlog_ptr = dlog.data_ptr()
         else:
             ldd = V

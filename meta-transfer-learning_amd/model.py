@@ -269,11 +269,11 @@ class Transformer(nn.Module):
     def _theta_for_forward(self):
         return self._theta if self._theta_override is None else self._theta_override
 
-    def _run_forward(self, theta, x, lengths, target, smoothing=0.0):
+    def _run_forward(self, theta, x, lengths, target, smoothing=0.0, **loss_kw):
         eng = self._need_engine()
         if x.device != theta.device:
             x = x.to(theta.device, non_blocking=True)
-        out = eng.forward(theta, x.float(), lengths, target, smoothing=smoothing)
+        out = eng.forward(theta, x.float(), lengths, target, smoothing=smoothing, **loss_kw)
         self._pass_token += 1
         self._last = out
         return out
@@ -289,14 +289,17 @@ class Transformer(nn.Module):
         return _ModelEncFn.apply(self._anchor, self, padded_input, input_lengths, padded_target)
 
     # fast path used by the trainer: no autograd objects at all
-    def pass_forward(self, x, lengths, target, theta=None, smoothing=0.0, lane=0):
+    def pass_forward(self, x, lengths, target, theta=None, smoothing=0.0, lane=0, loss_type='ce', percentages=None, target_sizes=None):
+        """loss_type 'ctc': the pass's loss (and the gradient pass_backward forms) is the CTC loss of `percentages` / `target_sizes`
+        (PassEngine.prepare_tasks) instead of the cross entropy"""
+        loss_kw = dict(loss_type=loss_type, percentages=percentages, target_sizes=target_sizes)
         if lane == 0:
-            return self._run_forward(self._theta if theta is None else theta, x, lengths, target, smoothing)
+            return self._run_forward(self._theta if theta is None else theta, x, lengths, target, smoothing, **loss_kw)
         self._need_engine()
         th = self._theta if theta is None else theta
         if x.device != th.device:
             x = x.to(th.device, non_blocking=True)
-        return self.engines[lane].forward(th, x.float(), lengths, target, smoothing=smoothing)
+        return self.engines[lane].forward(th, x.float(), lengths, target, smoothing=smoothing, **loss_kw)
 
     def pass_backward(self, grad=None, scale=1.0, lane=0, dmem_hook=None):
         self._need_engine()

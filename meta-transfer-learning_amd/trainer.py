@@ -348,6 +348,11 @@ def _sample_takes_need(ds):
     return 'need' in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
 
 
+def _check_loss_type(loss_type):
+    if loss_type not in ('ce', 'ctc'):
+        raise NotImplementedError("loss_type must be 'ce' or 'ctc'")
+
+
 class TransientTrainer():
     def __init__(self):
         logging.info('Transient Trainer is initialized')
@@ -395,15 +400,19 @@ class TransientTrainer():
         self.h2_check_every, self.h2_limit, self.h2_guard = 100, 1e-3, 'x3'
         self.h2_census, self._h2_iter, self._h2_buf, self._census_on = None, 0, None, None
         self._turn = 0
+        # the training objective of meta_iteration: 'ce', or 'ctc' (--loss ctc: the CTC loss of each batch's percentages and target
+        # sizes, utils/metrics.py:127-148).  train() sets it from its loss_type; part of every command-list key.
+        self.loss_type = 'ce'
 
     # ------------------------------------------------------------------ drop-in single-batch API
     def forward_one_batch(self, model, vocab, src, trg, src_percentages, src_lengths, trg_lengths, smoothing, loss_type,
                           verbose=False):
         """-> (loss tensor, total_cer, total_char); `loss.backward()` runs the HIP backward (transient_trainer.py:25-73).
         Same steps as the reference: model forward, calculate_metrics (label smoothing included), CER of the post-processed
-        strings; the ~2*B*T per-element `int(x)` device syncs become one D2H copy of gold / hyp."""
-        if loss_type != 'ce':
-            raise NotImplementedError("only loss_type='ce' is on the accelerated path")
+        strings; the ~2*B*T per-element `int(x)` device syncs become one D2H copy of gold / hyp.
+        loss_type 'ctc': the CTC loss of `sizes` decoder positions and `trg_lengths` labels per utterance (:38-41); a batch with an
+        utterance that has no alignment returns +inf, as the reference does ("Found infinity loss")."""
+        _check_loss_type(loss_type)
         pred, gold, hyp = model(src, src_lengths, trg, verbose=False)
         sizes = src_percentages.mul_(int(pred.size(1))).int()     # SURVEY Q6: the reference scales the caller's tensor in place
         loss, _ = calculate_metrics(pred, gold, vocab.PAD_ID, input_lengths=sizes, target_lengths=trg_lengths,
@@ -419,8 +428,10 @@ class TransientTrainer():
             return param_group['lr']
 
     # ------------------------------------------------------------------ one meta-iteration on the device
-    def meta_iteration(self, model, vocab, task_batches, val_batch, n_tasks, inner, outer, args, task_ids=None):
+    def meta_iteration(self, model, vocab, task_batches, val_batch, n_tasks, inner, outer, args, task_ids=None, loss_type=None):
         """task_batches: this rank's [(inputs, input_sizes, percentages, targets, target_sizes)], val_batch: same 5-tuple.
+        loss_type: 'ce' or 'ctc' (default: self.loss_type).  With 'ctc' every pass's loss is the CTC loss of its batch's percentages
+        and target sizes (a None there is derived from the lengths / the targets, PassEngine.prepare_tasks); label smoothing is ignored.
         n_tasks is the GLOBAL task count (the 1/n of the validation loss).  Leaves G in model._G; returns the read-backs.
         With several ranks and chunking on, the schedules that hook the validation backward leave model._G ALREADY summed over
         the ranks and set self._G_reduced (reset here on entry); a direct caller must check that flag -- or call
@@ -433,13 +444,16 @@ class TransientTrainer():
         theta0 = model.flat_parameters
         self._G_reduced = False
         smoothing = float(getattr(args, 'label_smoothing', 0.0) or 0.0)
+        lt = self.loss_type if loss_type is None else loss_type
+        _check_loss_type(lt)
+        ctc = lt == 'ctc'
         hooked = any(e.prof is not None or e.forward_hook is not None for e in model.engines)
         use_cmdlists = self.use_cmdlists and not hooked
         self.last_schedule = 'lanes'                         # (diagnostics / tests: which schedule the last iteration took)
         if self._can_batch(model, task_batches, val_batch):
             frames = [int(tb[0].shape[3]) for tb in task_batches]
             self.last_schedule = 'batched' if min(frames) == max(frames) else 'batched-ragged'
-            return self._batched_iteration(model, task_batches, val_batch, n_tasks, inner, args, smoothing, use_cmdlists)
+            return self._batched_iteration(model, task_batches, val_batch, n_tasks, inner, args, smoothing, use_cmdlists, lt)
         n_lanes = min(model.n_lanes, max(len(task_batches), 1))
         if len(task_batches) > n_lanes:                      # several rounds: equal rounds (8 tasks on 6 lanes measured slower than on 3)
             rounds = -(-len(task_batches) // n_lanes)
@@ -472,6 +486,7 @@ class TransientTrainer():
             with torch.cuda.stream(streams[lane]):
                 streams[lane].wait_event(ready)
                 bufs[lane][2].zero_()
+        ctc_kw = lambda pct, sizes: dict(percentages=pct, target_sizes=sizes) if ctc else {}
         for idx, (tx, tsz, _tp, ty, _tl) in enumerate(task_batches):      # enqueue task by task, alternating lanes
             lane = idx % n_lanes
             eng = model.engines[lane]
@@ -479,10 +494,11 @@ class TransientTrainer():
                 tx, t_own = widened(tx.to(dev, non_blocking=True), eng, 'lane.x_tr')
                 lw = (lambda y_: _label_width([y_], self.label_quantum, eng.hp.tgt_max_len)) if (q > 1 and self.label_quantum > 1) else (lambda y_: None)
                 eng.census = self._census_on[lane:lane + 1] if self._census_on is not None else None
-                m_tr = eng.prepare(tsz, ty, tx.shape[0], tx.shape[3], slot=0, frames=t_own, width=lw(ty))   # host ints -> static device buffers
-                m_va = eng.prepare(val_batch[1], val_batch[3], vx.shape[0], vx.shape[3], slot=1, frames=v_own, width=lw(val_batch[3]))
+                m_tr = eng.prepare(tsz, ty, tx.shape[0], tx.shape[3], slot=0, frames=t_own, width=lw(ty), **ctc_kw(_tp, _tl))   # host ints -> static device buffers
+                m_va = eng.prepare(val_batch[1], val_batch[3], vx.shape[0], vx.shape[3], slot=1, frames=v_own, width=lw(val_batch[3]),
+                                   **ctc_kw(val_batch[2], val_batch[4]))
                 slots = self._slots(model, lane, m_tr, m_va)
-                key = (lane, tuple(tx.shape), tuple(vx.shape), t_own is not None, v_own is not None, m_tr['Td'], m_va['Td'], n_tasks, bool(args.clip),
+                key = (lt, lane, tuple(tx.shape), tuple(vx.shape), t_own is not None, v_own is not None, m_tr['Td'], m_va['Td'], n_tasks, bool(args.clip),
                        float(args.max_norm), smoothing, float(inner.param_groups[0]['lr']), theta0.data_ptr(), eng.dropout_p,
                        tuple(b.data_ptr() for b in bufs[lane]), streams[lane].cuda_stream, eng.use_side_stream, eng.census is not None)
                 # a rank that holds ONE task (8 tasks on 8 GPUs): G = its g, handed to the all-reduce group by group under the backward
@@ -493,7 +509,7 @@ class TransientTrainer():
                         _lib.lib().mtl_axpy(st, G_.data_ptr() + 4 * lo, g_.data_ptr() + 4 * lo, 1.0, n), 'mtl_axpy'))
                     key = key + ('chunked',) if chunk is not None else key
                 body = lambda xa, xb: self._task_body(model, lane, bufs[lane], theta0, xa, m_tr, xb, m_va, n_tasks, inner, args,
-                                                      smoothing, slots, chunk)
+                                                      smoothing, slots, chunk, lt)
                 if use_cmdlists:
                     self._run_recorded(key, eng, tx, vx, body, on_break=chunk)
                 else:
@@ -553,7 +569,7 @@ class TransientTrainer():
         frames = [int(tb[0].shape[3]) for tb in task_batches]
         return min(frames) >= 4 and sum(frames) >= self.ragged_fill * len(frames) * max(frames)
 
-    def _batched_iteration(self, model, task_batches, val_batch, n_tasks, inner, args, smoothing, use_cmdlists):
+    def _batched_iteration(self, model, task_batches, val_batch, n_tasks, inner, args, smoothing, use_cmdlists, loss_type='ce'):
         """trainer/asr/transient_trainer.py:178-237 for all local tasks at once.  The tasks of a meta-step are independent given
         theta0, so their training passes run as ONE pass over nt x k_train samples (shared parameters; per-task losses and a
         (nt, P) stack of per-task gradients), the nt inner steps as one kernel into a (nt, P) stack of theta', and their
@@ -652,10 +668,13 @@ class TransientTrainer():
         _trace.mark('input_copies')
         wq = (ragged or varies) and self.ragged_quantum > 1 and self.label_quantum > 1      # label widths repeat like the frame counts
         lw = (lambda ys: _label_width(ys, self.label_quantum, eng.hp.tgt_max_len)) if wq else (lambda ys: None)
+        # ctc: every task's in_len comes from ITS percentages and ITS own decoder width, whatever width the stack is padded to
+        ctc_tr = dict(percentages=[tb[2] for tb in task_batches], target_sizes=[tb[4] for tb in task_batches]) if loss_type == 'ctc' else {}
+        ctc_va = dict(percentages=[val_batch[2]] * nt, target_sizes=[val_batch[4]] * nt) if loss_type == 'ctc' else {}
         m_tr = eng.prepare_tasks([(tsz, ty) for (_tx, tsz, _tp, ty, _tl) in task_batches], B, T, slot=0, frames=frames if own_tr else None,
-                                 width=lw([tb[3] for tb in task_batches]))
+                                 width=lw([tb[3] for tb in task_batches]), **ctc_tr)
         m_va = eng.prepare_tasks([(val_batch[1], val_batch[3])] * nt, vx_in.shape[0], Tv, slot=1, frames=[Tv_own] * nt if Tv != Tv_own else None,
-                                 width=lw([val_batch[3]]))
+                                 width=lw([val_batch[3]]), **ctc_va)
         _trace.mark('prepare_tasks')
         Bv = vx_in.shape[0]
         slots = dict(hyp_tr=eng.buf('slot.hyp_tr', (nt * B, m_tr['Td']), torch.int64), loss_tr=eng.buf('slot.loss_tr', (nt,)),
@@ -671,14 +690,15 @@ class TransientTrainer():
 
         def body(_xa=None, _xb=None):
             eng.zero_(g)                                                         # inner_opt.zero_grad()   (:198), every task
-            eng.forward_device(theta0, Xtr, m_tr, smoothing, hyp_out=slots['hyp_tr'], loss_out=slots['loss_tr'])      # (:188)
+            eng.forward_device(theta0, Xtr, m_tr, smoothing, hyp_out=slots['hyp_tr'], loss_out=slots['loss_tr'], loss_type=loss_type)      # (:188)
             eng.backward(g, 1.0, sG=total)                                       # tr_loss.backward()      (:199)
             if args.clip:
                 for t in range(nt):
                     clip_flat_grad_(model, g[t * total:(t + 1) * total], args.max_norm, lane=0)      # (:205-206)
             check(eng.lib.mtl_sgd_theta_prime_tasks(eng.stream, theta0.data_ptr(), g.data_ptr(), lr, theta1.data_ptr(), total, nt),
                   'mtl_sgd_theta_prime_tasks')                                   # inner_opt.step()        (:207)
-            eng.forward_device(theta1, Xva, m_va, smoothing, hyp_out=slots['hyp_va'], loss_out=slots['loss_va'], sP=total)   # (:215)
+            eng.forward_device(theta1, Xva, m_va, smoothing, hyp_out=slots['hyp_va'], loss_out=slots['loss_va'], sP=total,
+                               loss_type=loss_type)                              # (:215)
             eng.slice_hook = chunk
             try:
                 eng.backward(g, 1.0 / n_tasks, sG=total)                         # (val_loss/n).backward(): g_t += g_val,t/n (Q1)
@@ -687,7 +707,7 @@ class TransientTrainer():
             if chunk is None:
                 check(eng.lib.mtl_sum_tasks(eng.stream, G.data_ptr(), g.data_ptr(), total, nt, 0), 'mtl_sum_tasks')    # add_copy_grad() (:229)
 
-        key = ('batched', nt, (B, F, T), own_tr, tuple(Xva.shape), Tv != Tv_own, m_tr['Td'], m_va['Td'], n_tasks, bool(args.clip), float(args.max_norm),
+        key = ('batched', loss_type, nt, (B, F, T), own_tr, tuple(Xva.shape), Tv != Tv_own, m_tr['Td'], m_va['Td'], n_tasks, bool(args.clip), float(args.max_norm),
                smoothing, lr, theta0.data_ptr(), eng.dropout_p, g.data_ptr(), theta1.data_ptr(), G.data_ptr(),
                torch.cuda.current_stream(dev).cuda_stream, eng.use_side_stream, chunk is not None, eng.census is not None)
         _trace.mark('keys')
@@ -745,18 +765,19 @@ class TransientTrainer():
         self._chunks = None
         self._G_reduced = True
 
-    def _task_body(self, model, lane, bufs, theta0, x_tr, m_tr, x_va, m_va, n_tasks, inner, args, smoothing, slots, chunk=None):
+    def _task_body(self, model, lane, bufs, theta0, x_tr, m_tr, x_va, m_va, n_tasks, inner, args, smoothing, slots, chunk=None,
+                   loss_type='ce'):
         """Kernels of ONE task on the current stream (eager, or recorded into a command list): train pass at theta0, fused inner
         SGD into theta', validation pass at theta', accumulation into the lane's copy_grad buffer."""
         eng = model.engines[lane]
         g, theta1, G = bufs
         eng.zero_(g)                                                     # inner_opt.zero_grad()   (:198)
-        eng.forward_device(theta0, x_tr, m_tr, smoothing, hyp_out=slots['hyp_tr'], loss_out=slots['loss_tr'])   # meta-train forward (:188)
+        eng.forward_device(theta0, x_tr, m_tr, smoothing, hyp_out=slots['hyp_tr'], loss_out=slots['loss_tr'], loss_type=loss_type)   # meta-train forward (:188)
         eng.backward(g, 1.0)                                             # tr_loss.backward()      (:199)
         if args.clip:
             clip_flat_grad_(model, g, args.max_norm, lane=lane)          # (:205-206)
         eng.sgd_theta_prime(theta0, g, inner.param_groups[0]['lr'], theta1)     # inner_opt.step() (:207)
-        eng.forward_device(theta1, x_va, m_va, smoothing, hyp_out=slots['hyp_va'], loss_out=slots['loss_va'])   # meta-validation forward (:215)
+        eng.forward_device(theta1, x_va, m_va, smoothing, hyp_out=slots['hyp_va'], loss_out=slots['loss_va'], loss_type=loss_type)   # meta-validation forward (:215)
         eng.slice_hook = chunk                                           # (several ranks: G's groups leave for their all-reduce as they finish)
         try:
             eng.backward(g, 1.0 / n_tasks)                               # (val_loss/n).backward(): g += g_val/n (Q1)
@@ -941,8 +962,8 @@ class TransientTrainer():
     def train(self, model, vocab, train_data_list, valid_loader_list, loss_type, start_it, num_it, args, inner_opt=None,
               outer_opt=None, evaluate_every=1000, window_size=100, last_summary_every=1000, last_metrics=None, early_stop=10,
               cpu_state_dict=False, is_copy_grad=False):
-        if loss_type != 'ce':
-            raise NotImplementedError("only loss_type='ce' is on the accelerated path")
+        _check_loss_type(loss_type)
+        self.loss_type = loss_type                # what meta_iteration trains on; the validation loop gets it as an argument
         if not is_copy_grad:
             raise NotImplementedError('the accelerated path is the --copy-grad loop (is_copy_grad=True)')
         history = []
@@ -1108,8 +1129,7 @@ class JointTrainer():
         if discriminator is None:
             return TransientTrainer.forward_one_batch(self, model, vocab, src, trg, src_percentages, src_lengths, trg_lengths, smoothing,
                                                       loss_type, verbose=verbose)
-        if loss_type != 'ce':
-            raise NotImplementedError("only loss_type='ce' is on the accelerated path")
+        _check_loss_type(loss_type)
         pred, gold, hyp, enc_output = model.forward_with_encoder_output(src, src_lengths, trg)
         accent_pred = discriminator(enc_output)                         # discriminator(torch.sum(enc_output, dim=1))
         if multi_task:
@@ -1127,18 +1147,22 @@ class JointTrainer():
             return loss, total_cer, total_char, disc_loss
         return loss, total_cer, total_char, disc_loss, enc_loss
 
-    def run_iteration(self, model, vocab, task_batches, n_tasks, opt, args, discriminator=None, opt_disc=None, task_ids=None):
+    def run_iteration(self, model, vocab, task_batches, n_tasks, opt, args, discriminator=None, opt_disc=None, task_ids=None,
+                      loss_type='ce'):
         """One iteration over this rank's task batches.  discriminator / opt_disc: the accent head and its optimizer; task_ids: the
         tasks' indices among all n_tasks (their accent ids; default 0, 1, ...).  -> [total_loss, total_cer, total_char] and, with a
-        discriminator, total_disc_loss (weighted, as logged) and total_enc_loss."""
+        discriminator, total_disc_loss (weighted, as logged) and total_enc_loss.
+        loss_type 'ctc': every task's loss is the CTC loss of its batch's percentages and target sizes (joint_trainer.py:38-41)."""
         dev = model.flat_parameters.device
         g = model.flat_grad
         smoothing = float(getattr(args, 'label_smoothing', 0.0) or 0.0)
+        _check_loss_type(loss_type)
+        loss_kw = lambda pct, sizes: dict(loss_type='ctc', percentages=pct, target_sizes=sizes) if loss_type == 'ctc' else {}
         g.zero_()                                                       # opt.zero_grad()
         reads = []
         if discriminator is None:
             for (tx, tsz, _tp, ty, _tl) in task_batches:
-                out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing)
+                out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing, **loss_kw(_tp, _tl))
                 reads.append(_Readback(out, ('joint', len(reads), 0)))
                 model.pass_backward(g, 1.0 / n_tasks)                   # (tr_loss / n).backward()
         else:
@@ -1155,7 +1179,7 @@ class JointTrainer():
                     continue
                 w = 1.0 if not adversarial else (self.beta if decay else 0.5)
                 tx, tsz, _tp, ty, _tl = batch_of[m]
-                out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing)
+                out = model.pass_forward(tx.to(dev, non_blocking=True), tsz, ty, smoothing=smoothing, **loss_kw(_tp, _tl))
                 reads.append(_Readback(out, ('joint', len(reads), 0)))
                 losses = discriminator.head_forward(model.engine.encoder_output(), m, adversarial)
                 host = _pinned(('disc', len(disc_reads), 0), (2,), torch.float32)
@@ -1190,8 +1214,9 @@ class JointTrainer():
     def train(self, model, vocab, train_data_list, valid_loader_list, loss_type, start_it, num_it, args, evaluate_every=1000,
               window_size=100, last_summary_every=1000, last_metrics=None, early_stop=10, cpu_state_dict=False, is_copy_grad=False,
               opt_name='adam', discriminator=None):
-        if loss_type != 'ce' or opt_name != 'adam':
-            raise NotImplementedError("accelerated joint training: loss_type='ce', opt_name='adam'")
+        _check_loss_type(loss_type)
+        if opt_name != 'adam':
+            raise NotImplementedError("accelerated joint training: opt_name='adam'")
         if discriminator is not None:
             model._need_engine()
         if discriminator is not None and discriminator.flat_parameters.device != model.flat_parameters.device:
@@ -1242,6 +1267,8 @@ class JointTrainer():
                 popped = [buf[m].pop() for m in range(n_tasks)]
                 # (without a discriminator the call carries the six positional arguments it always has)
                 disc_kw = {} if discriminator is None else dict(discriminator=discriminator, opt_disc=opt_disc, task_ids=my_tasks)
+                if loss_type != 'ce':
+                    disc_kw['loss_type'] = loss_type
                 totals = self.run_iteration(model, vocab, [popped[m][0] for m in my_tasks], n_tasks, opt, args, **disc_kw)
                 total_loss, total_cer, total_char = totals[:3]
                 total_disc_loss, total_enc_loss = totals[3:] if discriminator is not None else (None, None)
