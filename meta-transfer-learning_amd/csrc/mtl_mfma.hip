@@ -1037,13 +1037,45 @@ __device__ __forceinline__ void x3_amax_raise(float* a, float mx) {
     if ((threadIdx.x & 63) == 0 && mx > *slot) atomicMax(reinterpret_cast<unsigned*>(slot), __float_as_uint(mx));
 }
 
+// The two-piece fp16 instantiations with 64 px x 64 ch consumer waves whose epilogue runs in the SLIM form (kernel header) besides the
+// 64-channel data gradients (WN = 1): the forwards of conv2 (BN = 64, WN = 1: ReLU and ReLU + pool) and conv5 (BN = 128, WN = 2: ReLU),
+// and conv7's un-pooling data gradient.  A form is listed only while it measures faster than store4x2 / gate4x2 + store4x2g on isolated
+// launches (profiles/conv_fwd_epilogue/kernel_ab.txt): conv7's ReLU + pool forward (BN = 128, POOL) compiled to 129 registers without
+// scratch in this form too, but ran 1.871 against 1.867 ms, and keeps the epilogue it had.
+template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN>
+constexpr bool x3h_slim_fwd() {
+    return X3H_M16 != 0 && NP == 2 && G == 2 && !UNPOOL &&
+           ((BN == 64 && WN == 1 && EPI != EPI_DGRAD) || (BN == 128 && WN == 2 && EPI == EPI_RELU));
+}
+template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN>
+constexpr bool x3h_slim_dg128() {
+    return NP == 2 && G == 2 && UNPOOL && EPI == EPI_DGRAD && BN == 128 && WN == 2;
+}
+// A SLIM epilogue adds ONE 32-bit byte offset per lane to a scalar base: at most 15 frequency positions (a clamped gate row) of `ch`
+// channels plus the lane's column inside the wave's 64.  A pure function of the shape; shapes beyond it take the WIDE (64-bit) twin.
+constexpr bool x3h_lane_offsets_fit(long ch) { return (15 * ch + 64) * 4 < (1L << 32); }
+static_assert(x3h_lane_offsets_fit(128) && x3h_lane_offsets_fit(71582783) && !x3h_lane_offsets_fit(71582784), "just below / at the limit");
+static_assert((15 * 71582783L + 63) * 4 + 7 <= 0xffffffffL, "the last byte a lane offset reaches below the limit");
+
 // WN = consumer waves along the output channels of a 128-pixel sub-tile (2 pixel halves x WN): 2 -> each wave owns 64 px x BN/2 ch,
 // 1 -> 64 px x BN ch.  The fragment reads of a wave feed TM x TN MFMA groups, (TM + TN) NP ds_read_b128 per TM TN groups: with
 // 64 output channels WN = 2 means 3 reads per group (two-piece fp16: LDS 100 % busy at 50 % matrix-pipe load), WN = 1 means 2.
-template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN>
+// WIDE: the instantiation's twin with the 64-bit per-element addresses of store4 / store4x2 / gate4 (shapes x3h_lane_offsets_fit refuses)
+template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN, bool WIDE = false>
 __global__ __launch_bounds__((2 * WN * G + 4) * 64) __attribute__((amdgpu_waves_per_eu(WN == 1 ? 4 : 1)))   // WN = 1: two workgroups per CU
 void conv3x3_x3h_kernel(ConvX3P p) {
-    constexpr bool SLIM = WN == 1 && EPI == EPI_DGRAD;             // 64 x 64 wave tiles + gated epilogue: every register counts (x3_wave_max, the epilogue)
+    // SLIM: 64 x 64 wave tiles whose epilogue has no register to spare.  (a) wave maxima from ds_swizzle (x3_wave_max: no lane-index
+    // registers across the matrix loop); (b) the epilogue addresses every access as scalar base + one 32-bit lane offset, with the lane
+    // terms re-derived from the lane index inside the epilogue (SLIM_FWD: the ReLU / pool forms, SLIM_DG: the gated form).
+    // SLIM_HALO: the halo waves keep their validity bits in one register and re-derive the elements' lane terms at the fetch and at
+    // the commit, and (SLIM_H32) fetch a pooled source with 32-bit offsets (launcher guard of its own).  Only the data gradients, whose
+    // un-pooling halo waves otherwise spill (conv7's: 56 bytes): the re-derivation sits in the commit, between the two barriers of a
+    // halo swap, and cost the forwards 5 % (their halo waves carry no arg-max codes and fit without it).
+    constexpr bool SLIM_FWD = !WIDE && x3h_slim_fwd<BN, G, UNPOOL, EPI, NP, WN>();
+    constexpr bool SLIM_H32 = WN == 1 && EPI == EPI_DGRAD;
+    constexpr bool SLIM_DG = SLIM_H32 || (!WIDE && x3h_slim_dg128<BN, G, UNPOOL, EPI, NP, WN>());
+    constexpr bool SLIM_HALO = SLIM_DG;
+    constexpr bool SLIM = SLIM_DG || SLIM_FWD;
     constexpr int CW = 2 * WN;                                      // consumer waves per 8 x 16 sub-tile
     constexpr int WTM = 64, WTN = BN / WN, TM = WTM / 32, TN = WTN / 32;
     constexpr int XH_HT = 8 * G + 2, XH_NPIX = XH_HT * XH_HF;      // halo of an (8 G) x 16 tile
@@ -1080,12 +1112,12 @@ void conv3x3_x3h_kernel(ConvX3P p) {
         };
         float4 hv[XH_NVA];
         uchar4 ha[XH_NVA];
-        unsigned hm[SLIM ? 1 : XH_NVA];        // SLIM: the validity bits of all elements in hm[0] (the window position is re-derived at the commit)
+        unsigned hm[SLIM_HALO ? 1 : XH_NVA];        // SLIM_HALO: the validity bits of all elements in hm[0] (the window position is re-derived at the commit)
         auto fetch_halo = [&](int q) {          // stage q: channels c*32 .. +31 of the halo pixels of its tile
             const int j = q / cch, c = q - j * cch;
             const X3Tile tl = x3_tile<G>(p, blockIdx.x + j * gridDim.x, cur_halo);
-            int pt = ptid;                      // (SLIM: the elements' lane terms are derived here, not kept -- spilled -- from the prologue)
-            if constexpr (SLIM) asm volatile("" : "+v"(pt));
+            int pt = ptid;                      // (SLIM_HALO: the elements' lane terms are derived here, not kept -- spilled -- from the prologue)
+            if constexpr (SLIM_HALO) asm volatile("" : "+v"(pt));
 #pragma unroll
             for (int i = 0; i < XH_NVA; ++i) {
                 const int e = pt + i * NHALO;
@@ -1096,12 +1128,12 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                 const int tc = min(max(ts, 0), T - 1), fc = min(max(fs, 0), F - 1);
                 if (!UNPOOL) {
                     hv[i] = *reinterpret_cast<const float4*>(p.x + (((long)tl.b * T + tc) * F + fc) * Cin + c * BK + c4);
-                    if constexpr (SLIM) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
+                    if constexpr (SLIM_HALO) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
                     else hm[i] = ok ? 1u : 0u;
                 } else {
                     const int tp = tc >> 1, fp = fc >> 1;
                     ok = ok && tp < Tp && fp < Fp;
-                    if constexpr (SLIM) {       // scalar base of the (sample, chunk) + one 32-bit offset for both loads: no 64-bit address pair per element
+                    if constexpr (SLIM_H32) {   // scalar base of the (sample, chunk) + one 32-bit offset for both loads: no 64-bit address pair per element
                         const long sbase = (long)__builtin_amdgcn_readfirstlane(tl.b) * Tp * Fp * Cin + c * BK;
                         const unsigned o = (unsigned)((min(tp, Tp - 1) * Fp + min(fp, Fp - 1)) * Cin + c4);
                         ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + sbase + o);
@@ -1111,7 +1143,7 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                     ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + o);
                     hv[i] = *reinterpret_cast<const float4*>(p.x + o);
                     }
-                    if constexpr (SLIM) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
+                    if constexpr (SLIM_HALO) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
                     else hm[i] = (ok ? 1u : 0u) | ((unsigned)(((fs & 1) << 1) | (ts & 1)) << 1);
                 }
             }
@@ -1120,19 +1152,19 @@ void conv3x3_x3h_kernel(ConvX3P p) {
         // extra live registers spill under the 168-VGPR cap of a 12-wave workgroup and every launch gets 15-40 % slower.)
         auto commit_halo = [&]() {
             int pt = ptid;
-            if constexpr (SLIM) asm volatile("" : "+v"(pt));
+            if constexpr (SLIM_HALO) asm volatile("" : "+v"(pt));
 #pragma unroll
             for (int i = 0; i < XH_NVA; ++i) {
                 const int e = pt + i * NHALO;
                 if ((e >> 3) >= XH_NPIX) continue;
                 float4 v = hv[i];
-                const bool ok = SLIM ? (hm[0] >> i) & 1u : hm[i] & 1u;
+                const bool ok = SLIM_HALO ? (hm[0] >> i) & 1u : hm[i] & 1u;
                 if (!UNPOOL) {
                     v = mask4(v, ok ? 15u : 0u);
                 } else {
                     // (tile origins are even: the parities of ts = t0 + ht - 1 and fs = f0 + hf - 1 are those of ht + 1 and hf + 1)
                     const int ht_ = (e >> 3) / XH_HF, hf_ = (e >> 3) - ht_ * XH_HF;
-                    const unsigned sub = SLIM ? (unsigned)((((hf_ + 1) & 1) << 1) | ((ht_ + 1) & 1)) : hm[SLIM ? 0 : i] >> 1;
+                    const unsigned sub = SLIM_HALO ? (unsigned)((((hf_ + 1) & 1) << 1) | ((ht_ + 1) & 1)) : hm[SLIM_HALO ? 0 : i] >> 1;
                     v.x = (ok && ha[i].x == sub) ? v.x : 0.f;
                     v.y = (ok && ha[i].y == sub) ? v.y : 0.f;
                     v.z = (ok && ha[i].z == sub) ? v.z : 0.f;
@@ -1277,6 +1309,14 @@ void conv3x3_x3h_kernel(ConvX3P p) {
     auto raise_bound = [&]() {
         if (!p.amax_out) return;
         float bmax = 0.f;
+        if constexpr (SLIM_FWD) {          // the task's bias from its index and the lane's column from a re-read lane index: kept from the
+            int c15;                       // prologue, the per-task pointer and the lane's bias addresses are spilled across the matrix loop
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(c15));
+            const float* bias_k = p.bias + (long)cur_task * p.sBias + wn * WTN + 2 * (c15 & 15);
+#pragma unroll
+            for (int jn = 0; jn < TN16; ++jn)
+                for (int nt = 0; nt < p.ntile; ++nt) bmax = fmaxf(bmax, fabsf(bias_k[nt * BN + (jn >> 1) * 32 + (jn & 1)]));
+        } else
         if (EPI != EPI_DGRAD) {
             if (M16) {
 #pragma unroll
@@ -1444,11 +1484,79 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                                 epi.store4(wm * WTM + i * 32 + 8 * g + 4 * hi, wn * WTN + jn * 32 + l31, v);
                             }
                 };
-                if (EPI == EPI_RELU) {
+                if constexpr (SLIM_FWD) {
+                    // EpiConvRelu::store4x2 / EpiConvPool::store4x2 in the SLIM addressing form (the data-gradient branch below explains it):
+                    // the sample, the tile, the wave's rows and channel block, the accumulator group and the task are wave-uniform, so a store
+                    // is a scalar base + ONE 32-bit lane offset (the pooled value and its arg-max pair share it: x 4 and x 1), the bias pairs
+                    // of the wave's two 32-channel blocks come from a scalar base + the lane's column and are requested once per tile, ahead
+                    // of the first group.  Per element the arithmetic and its order are store4x2's: * inv, max|v|, + bias, max(., 0), the
+                    // first maximum in window order, the same predicates.
+                    int el;
+                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el));
+                    const int sb = __builtin_amdgcn_readfirstlane(tl.b), sf0 = __builtin_amdgcn_readfirstlane(tl.f0);
+                    const int st0 = __builtin_amdgcn_readfirstlane(ts0 + 4 * wm), sn0 = __builtin_amdgcn_readfirstlane(n0 + wn * WTN);
+                    const float* sbias = p.bias + ((long)__builtin_amdgcn_readfirstlane(cur_task) * p.sBias + sn0);
+                    const unsigned lcol = 2 * (el & 15);
+                    f32x2v bb[TN16 / 2];
+#pragma unroll
+                    for (int jp = 0; jp < TN16 / 2; ++jp)
+                        bb[jp] = *reinterpret_cast<const f32x2v*>(reinterpret_cast<const char*>(sbias + jp * 32) + lcol * 4u);
+                    if constexpr (EPI == EPI_RELU) {
+                        // rows of group i: t = st0 + 2 (i >> 1) + (k & 1); f = sf0 + fu + fl (fu: group and k, fl: lane)
+                        const int fl = 2 * (el >> 4);
+                        const unsigned so = (unsigned)(fl * Cout + lcol) * 4u;
+#pragma unroll
+                        for (int i = 0; i < TM16; ++i)
+#pragma unroll
+                            for (int jp = 0; jp < TN16 / 2; ++jp)
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const float v0 = acc4[i][2 * jp][k] * inv, v1 = acc4[i][2 * jp + 1][k] * inv;
+                                    mx = fmaxf(mx, fmaxf(fabsf(v0), fabsf(v1)));
+                                    asm volatile("" : "+v"(mx));      // (pinned, as in the data-gradient branch)
+                                    const int t = st0 + 2 * (i >> 1) + (k & 1), fu = 8 * (i & 1) + (k >> 1);
+                                    const f32x2v o = {fmaxf(v0 + bb[jp].x, 0.f), fmaxf(v1 + bb[jp].y, 0.f)};
+                                    if (t < T && sf0 + fu + fl < F)
+                                        __builtin_nontemporal_store(o, reinterpret_cast<f32x2v*>(reinterpret_cast<char*>(
+                                            p.y + ((((long)sb * T + t) * F + sf0 + fu) * Cout + sn0 + jp * 32)) + so));
+                                }
+                    } else {
+                        // window of group i: tp = st0 / 2 + (i >> 1); fp = sf0 / 2 + 4 (i & 1) + (lane >> 4)
+                        const int flp = el >> 4;
+                        const unsigned so = (unsigned)(flp * Cout) + lcol;          // in elements
+#pragma unroll
+                        for (int i = 0; i < TM16; ++i)
+#pragma unroll
+                            for (int jp = 0; jp < TN16 / 2; ++jp) {
+                                float v0[4], v1[4];
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    v0[k] = acc4[i][2 * jp][k] * inv;
+                                    v1[k] = acc4[i][2 * jp + 1][k] * inv;
+                                    mx = fmaxf(mx, fmaxf(fabsf(v0[k]), fabsf(v1[k])));
+                                }
+                                asm volatile("" : "+v"(mx));
+                                const int tp = (st0 >> 1) + (i >> 1), fpu = (sf0 >> 1) + 4 * (i & 1);
+                                if (tp < Tp && fpu + flp < Fp) {
+                                    float best0 = fmaxf(v0[0] + bb[jp].x, 0.f), best1 = fmaxf(v1[0] + bb[jp].y, 0.f);
+                                    int idx0 = 0, idx1 = 0;
+#pragma unroll
+                                    for (int k = 1; k < 4; ++k) {
+                                        const float x0 = fmaxf(v0[k] + bb[jp].x, 0.f), x1 = fmaxf(v1[k] + bb[jp].y, 0.f);
+                                        if (x0 > best0) best0 = x0, idx0 = k;
+                                        if (x1 > best1) best1 = x1, idx1 = k;
+                                    }
+                                    const long e = (((long)sb * Tp + tp) * Fp + fpu) * Cout + sn0 + jp * 32;
+                                    *reinterpret_cast<float2*>(reinterpret_cast<char*>(p.y + e) + so * 4u) = make_float2(best0, best1);
+                                    *reinterpret_cast<unsigned short*>(p.am_out + e + so) = (unsigned short)(idx0 | (idx1 << 8));
+                                }
+                            }
+                    }
+                } else if (EPI == EPI_RELU) {
                     walk(EpiConvRelu{p.y, bias_t, tl.b, ts0, tl.f0, T, F, Cout, n0});
                 } else if (EPI == EPI_POOL) {
                     walk(EpiConvPool{p.y, p.am_out, bias_t, tl.b, ts0, tl.f0, Tp, Fp, Cout, n0});
-                } else if constexpr (WN == 1 && EPI == EPI_DGRAD) {
+                } else if constexpr (SLIM_DG) {
                     // 64 px x 64 ch wave tiles under 128 registers: 64 accumulators leave no room for all 64 gate values and a 64-bit address
                     // per load and store.  (a) Addresses: everything but the lane's own column / frequency term is wave-uniform (the tile,
                     // the wave's rows, the accumulator group), so every access is a scalar base + ONE 32-bit lane offset, and the lane terms
@@ -1460,7 +1568,7 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                     int el;
                     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el));
                     const int sb = __builtin_amdgcn_readfirstlane(tl.b), sf0 = __builtin_amdgcn_readfirstlane(tl.f0);
-                    const int st0 = __builtin_amdgcn_readfirstlane(ts0 + 4 * wm), sn0 = __builtin_amdgcn_readfirstlane(n0);
+                    const int st0 = __builtin_amdgcn_readfirstlane(ts0 + 4 * wm), sn0 = __builtin_amdgcn_readfirstlane(n0 + wn * WTN);
                     // rows of the wave's group at 32-row block ib: t = st0 + 2 ib + (j & 1); f = sf0 + fu + fl (fu: group and j, fl: lane)
                     auto gate_base = [&](int t, int cb) {          // clamped row, columns from cb
                         return reinterpret_cast<const char*>(p.act + ((((long)sb * T + min(t, T - 1)) * F + sf0) * Cout + sn0 + cb));
@@ -1613,11 +1721,15 @@ void conv3x3_x3h_kernel(ConvX3P p) {
     raise_bound();
 }
 
-template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN = 2>
+template <int BN, int G, bool UNPOOL, int EPI, int NP, int WN = 2, bool WIDE = false>
 int launch_conv_x3h(ConvX3P p, int Te, int Fe, hipStream_t s) {
+    // the SLIM epilogues of the forwards and of conv7's data gradient add 32-bit lane offsets: a shape they cannot address runs the WIDE twin
+    if constexpr (!WIDE && (x3h_slim_fwd<BN, G, UNPOOL, EPI, NP, WN>() || x3h_slim_dg128<BN, G, UNPOOL, EPI, NP, WN>())) {
+        if (!x3h_lane_offsets_fit(p.g.Cout)) return launch_conv_x3h<BN, G, UNPOOL, EPI, NP, WN, true>(p, Te, Fe, s);
+    }
     constexpr int SMEM = NP * (8 * G + 2) * XH_HF * X3_ROWB + 3 * NP * BN * 64;
     constexpr int THREADS = (2 * WN * G + 4) * 64;
-    static int attr = set_smem(conv3x3_x3h_kernel<BN, G, UNPOOL, EPI, NP, WN>, SMEM);
+    static int attr = set_smem(conv3x3_x3h_kernel<BN, G, UNPOOL, EPI, NP, WN, WIDE>, SMEM);
     if (attr) return attr;
     static const int per_cu = (THREADS <= 512 && SMEM <= 80 * 1024) ? 2 : 1;     // 12-wave workgroups never share a CU
     static const int ncu = device_cu_count();
@@ -1630,7 +1742,7 @@ int launch_conv_x3h(ConvX3P p, int Te, int Fe, hipStream_t s) {
     p.tiles = p.ntf * p.ntt * p.g.B * p.ntile;
     if (p.tiles <= 0) return MTL_OK;                           // empty extent (a pooled forward with T < 2 or F < 2): no output, no launch
     const int grid = p.tiles < ncu * per_cu ? p.tiles : ncu * per_cu;
-    hipLaunchKernelGGL((conv3x3_x3h_kernel<BN, G, UNPOOL, EPI, NP, WN>), dim3(grid), dim3(THREADS), SMEM, s, p);
+    hipLaunchKernelGGL((conv3x3_x3h_kernel<BN, G, UNPOOL, EPI, NP, WN, WIDE>), dim3(grid), dim3(THREADS), SMEM, s, p);
     MTL_CHECK_LAUNCH();
     return MTL_OK;
 }
@@ -1650,6 +1762,8 @@ int dispatch_conv_x3(ConvX3P& p, int Te, int Fe, hipStream_t s) {
     // source, 64 reduction channels) 2.93 -> 2.46 ms, conv5's (dense, 128) 1.33 -> 1.24 ms, both bit for bit what the 32-channel waves
     // gave; their gated epilogue fits the 128 registers of this shape in the SLIM form of the kernel (before: spills, 0.45 -> 0.71 ms).
     // 8 x 16 tiles with two 64 x 64 waves (G = 1, WN = 1) measured 3.47 ms on conv2's.  The other two classes keep their routes (not measured).
+    // The forwards' epilogue in the SLIM form as well (x3h_slim_fwd; before: 144 / 160 bytes of scratch): conv2 + pool 2.21 -> 2.09 ms per
+    // 8-task launch, without pool 2.64 -> 2.36, bit for bit.
     if constexpr (NP == 2 && EPI != EPI_DGRAD) return launch_conv_x3h<64, 2, UNPOOL, EPI, NP, 1>(p, Te, Fe, s);
     if constexpr (NP == 2 && UNPOOL && X3H_DG2 != 0) {         // (the SLIM halo fetch addresses a pooled sample with 32-bit byte offsets)
         if (p.g.Cin == 64 && (long)p.g.Tp * p.g.Fp * p.g.Cin < (1L << 30)) return launch_conv_x3h<64, 2, UNPOOL, EPI, NP, 1>(p, Te, Fe, s);
