@@ -620,6 +620,23 @@ long mtl_lm_nll_workspace(int R, int V);
 int mtl_lm_nll_fwd(void* stream, const float* x, int ldx, const float* W, const float* bias, const long* target, int R, int H, int V,
                    int B, float* row_nll, float* seq_nll, void* ws, long ws_bytes);
 
+/* ---- LM evaluation (csrc/mtl_lstm.hip; lm/test.py:189-368 evaluate / evaluate_test): what follows mtl_lm_nll_fwd's row_nll ----------
+ * mtl_lm_switch_keys: the language-transition class of every (input word, target word) pair.  ids, target (R) int64; lang (V) bytes,
+ * 1 = a Chinese word, 0 = any other.  key[r] = -1 when target[r] < 0, when either id is outside [0, V) or when either id equals eos_id
+ * (the reference skips pairs that touch <eos>); else (lang[ids[r]] ? 0 : 2) + (lang[target[r]] ? 0 : 1): 0 = zh->zh, 1 = zh->en,
+ * 2 = en->zh, 3 = en->en.
+ * mtl_nll_key_sum: sum[k] = sum of row_nll[r] over the rows with key k, accumulated in fp64, count[k] = the number of those rows.  With
+ * key == NULL the key of row r is r / seg_rows (equal segments, the last one ragged: the window sums of an evaluation).  Rows whose key
+ * is outside [0, nkey) are skipped; every sum[k] and count[k] is written (0 for a key without rows).  No atomics: each key's rows are
+ * added by one owner thread per block of 256 rows in row order and the blocks are merged in block order, so the results are
+ * bit-identical from run to run.  -22 for nkey > MTL_NLL_MAX_KEYS, R < 1, nkey < 1, seg_rows < 1 with a null key, a null operand or a
+ * workspace below mtl_nll_key_sum_workspace(R, nkey) bytes (8-byte aligned device memory). */
+#define MTL_NLL_MAX_KEYS 4096
+int mtl_lm_switch_keys(void* stream, const long* ids, const long* target, const unsigned char* lang, long eos_id, int R, int V, int* key);
+long mtl_nll_key_sum_workspace(int R, int nkey);
+int mtl_nll_key_sum(void* stream, const float* row_nll, const int* key, int seg_rows, int R, int nkey, double* sum, int* count, void* ws,
+                    long ws_bytes);
+
 /* ---- device-resident beam search (csrc/mtl_beam.hip; modules/decoder.py:187-291 Decoder.beam_search) --------------------------
  * A chunk of U utterances is searched at once: W hypothesis rows per utterance, row u W + r of every (U W, ...) operand.
  * Limits (anything beyond is refused with -22): 1 <= W <= MTL_BEAM_MAX_W, W <= V <= MTL_BEAM_MAX_V, 1 <= S <= MTL_BEAM_MAX_S

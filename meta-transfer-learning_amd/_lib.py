@@ -147,6 +147,9 @@ SIGNATURES = {
     'mtl_gru_layer_bwd': (I, [P, P, P, F, P, P, P, P, P, I, I, I, P]),
     'mtl_lm_nll_workspace': (L, [I, I]),
     'mtl_lm_nll_fwd': (I, [P, P, I, P, P, P, I, I, I, I, P, P, P, L]),
+    'mtl_lm_switch_keys': (I, [P, P, P, P, L, I, I, P]),
+    'mtl_nll_key_sum_workspace': (L, [I, I]),
+    'mtl_nll_key_sum': (I, [P, P, P, I, I, I, P, P, P, L]),
     'mtl_beam_state_words': (L, [I, I, I]),
     'mtl_beam_rank': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I]),
     'mtl_beam_gather': (I, [P, P, I, P, P, L, I, I, I, L]),

@@ -743,16 +743,29 @@ __global__ __launch_bounds__(256) void lm_nll_partial_kernel(const float* __rest
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // the operands of a stage are fetched into registers while the matrix instructions of the stage before run (same values, same
+        // order of the arithmetic: the results do not change)
+        float px[NLL_RT * NLL_KT / 256], pw[NLL_RT * NLL_KT / 256];
+        auto fetch = [&](int k0) {
+#pragma unroll
+            for (int e = 0; e < NLL_RT * NLL_KT / 256; ++e) {
+                const int idx = tid + 256 * e, kk = idx & (NLL_KT - 1), rr = idx / NLL_KT;
+                const int k = k0 + kk, row = r0 + rr, col = c0 + rr;
+                px[e] = (row < R && k < H) ? x[(long)row * ldx + k] : 0.f;
+                pw[e] = (col < c_end && k < H) ? W[(long)col * H + k] : 0.f;
+            }
+        };
+        fetch(0);
         for (int k0 = 0; k0 < H; k0 += NLL_KT) {
             __syncthreads();                              // the previous stage's operands (and the previous block's logits) are consumed
 #pragma unroll
             for (int e = 0; e < NLL_RT * NLL_KT / 256; ++e) {
                 const int idx = tid + 256 * e, kk = idx & (NLL_KT - 1), rr = idx / NLL_KT;
-                const int k = k0 + kk, row = r0 + rr, col = c0 + rr;
-                xs[kk][rr] = (row < R && k < H) ? x[(long)row * ldx + k] : 0.f;
-                wsm[kk][rr] = (col < c_end && k < H) ? W[(long)col * H + k] : 0.f;
+                xs[kk][rr] = px[e];
+                wsm[kk][rr] = pw[e];
             }
             __syncthreads();
+            if (k0 + NLL_KT < H) fetch(k0 + NLL_KT);
 #pragma unroll
             for (int kk = 0; kk < NLL_KT; kk += 4) {
                 float a[2], b[2];
@@ -830,9 +843,104 @@ __global__ __launch_bounds__(256) void lm_nll_seq_kernel(const float* __restrict
     seq_nll[b] = acc;
 }
 
+// ---- LM evaluation: language-transition keys and keyed fp64 sums of the row NLLs -----------------------------------------------------
+constexpr int KEYSUM_ROWS = 256;      // rows per workgroup of the partial pass (1024: 4 x the serial walk per owner thread, 0.14 ms at R = 8050)
+
+__global__ __launch_bounds__(256) void lm_switch_keys_kernel(const long* __restrict__ ids, const long* __restrict__ target,
+                                                            const unsigned char* __restrict__ lang, long eos_id, int R, int V,
+                                                            int* __restrict__ key) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const long a = ids[r], b = target[r];
+    int k = -1;
+    if (a >= 0 && a < V && b >= 0 && b < V && a != eos_id && b != eos_id) k = (lang[a] ? 0 : 2) + (lang[b] ? 0 : 1);
+    key[r] = k;
+}
+
+// One workgroup per KEYSUM_ROWS rows.  Thread t owns the keys k with k % 256 == t: it alone walks the chunk in row order and adds the rows
+// of its keys (a run of equal keys in a register, flushed into the LDS slot of the key when the run ends), so no two threads ever touch
+// one accumulator and the order of the additions is a function of the data alone.  part_sum / part_cnt: [workgroup][nkey].
+__global__ __launch_bounds__(256) void nll_key_partial_kernel(const float* __restrict__ row_nll, const int* __restrict__ key, int seg_rows,
+                                                             int R, int nkey, double* __restrict__ part_sum, int* __restrict__ part_cnt) {
+    extern __shared__ double keysum_lds[];
+    double* lsum = keysum_lds;                                                  // [nkey]
+    float* sval = reinterpret_cast<float*>(lsum + nkey);                        // [KEYSUM_ROWS]
+    int* skey = reinterpret_cast<int*>(sval + KEYSUM_ROWS);                     // [KEYSUM_ROWS]
+    int* lcnt = skey + KEYSUM_ROWS;                                             // [nkey]
+    const int tid = threadIdx.x;
+    const long r0 = (long)blockIdx.x * KEYSUM_ROWS;
+    const int n = (int)min((long)KEYSUM_ROWS, (long)R - r0);
+    for (int k = tid; k < nkey; k += 256) lsum[k] = 0.0, lcnt[k] = 0;
+    for (int i = tid; i < n; i += 256) {
+        const long r = r0 + i;
+        const long k = key ? (long)key[r] : r / seg_rows;
+        skey[i] = (k >= 0 && k < nkey) ? (int)k : -1;
+        sval[i] = row_nll[r];
+    }
+    __syncthreads();
+    if (tid < nkey) {
+        int ck = -1, cc = 0;
+        double cs = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const int k = skey[i];
+            if (k < 0 || (k & 255) != tid) continue;
+            if (k != ck) {
+                if (ck >= 0) lsum[ck] += cs, lcnt[ck] += cc;
+                ck = k, cs = 0.0, cc = 0;
+            }
+            cs += (double)sval[i];
+            ++cc;
+        }
+        if (ck >= 0) lsum[ck] += cs, lcnt[ck] += cc;
+    }
+    __syncthreads();
+    double* ps = part_sum + (long)blockIdx.x * nkey;
+    int* pc = part_cnt + (long)blockIdx.x * nkey;
+    for (int k = tid; k < nkey; k += 256) ps[k] = lsum[k], pc[k] = lcnt[k];
+}
+
+__global__ __launch_bounds__(256) void nll_key_merge_kernel(const double* __restrict__ part_sum, const int* __restrict__ part_cnt, int nblk,
+                                                           int nkey, double* __restrict__ sum, int* __restrict__ count) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nkey) return;
+    double s = 0.0;
+    int c = 0;
+    for (int b = 0; b < nblk; ++b) s += part_sum[(long)b * nkey + k], c += part_cnt[(long)b * nkey + k];     // workgroup order
+    sum[k] = s;
+    count[k] = c;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mtl_lm_switch_keys(void* stream, const long* ids, const long* target, const unsigned char* lang, long eos_id, int R, int V, int* key) {
+    if (!ids || !target || !lang || !key || R < 1 || V < 1) return MTL_EINVAL;
+    hipLaunchKernelGGL(lm_switch_keys_kernel, dim3((R + 255) / 256), dim3(256), 0, as_stream(stream), ids, target, lang, eos_id, R, V, key);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
+
+long mtl_nll_key_sum_workspace(int R, int nkey) {
+    if (R < 1 || nkey < 1 || nkey > MTL_NLL_MAX_KEYS) return MTL_EINVAL;
+    return (long)((R + KEYSUM_ROWS - 1) / KEYSUM_ROWS) * nkey * 12;
+}
+
+int mtl_nll_key_sum(void* stream, const float* row_nll, const int* key, int seg_rows, int R, int nkey, double* sum, int* count, void* ws,
+                    long ws_bytes) {
+    if (!row_nll || !sum || !count || !ws || R < 1 || nkey < 1 || nkey > MTL_NLL_MAX_KEYS || (!key && seg_rows < 1)) return MTL_EINVAL;
+    if (ws_bytes < mtl_nll_key_sum_workspace(R, nkey) || (reinterpret_cast<uintptr_t>(ws) & 7)) return MTL_EINVAL;
+    const int nblk = (R + KEYSUM_ROWS - 1) / KEYSUM_ROWS;
+    hipStream_t s = as_stream(stream);
+    double* part_sum = static_cast<double*>(ws);
+    int* part_cnt = reinterpret_cast<int*>(part_sum + (long)nblk * nkey);
+    const size_t lds = (size_t)nkey * 12 + KEYSUM_ROWS * 8;                       // <= 50 KiB at MTL_NLL_MAX_KEYS
+    hipLaunchKernelGGL(nll_key_partial_kernel, dim3(nblk), dim3(256), lds, s, row_nll, key, key ? 1 : seg_rows, R, nkey, part_sum, part_cnt);
+    MTL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nll_key_merge_kernel, dim3((nkey + 255) / 256), dim3(256), 0, s, part_sum, part_cnt, nblk, nkey, sum, count);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
 
 long mtl_lm_nll_workspace(int R, int V) {
     if (R <= 0 || V <= 0) return 0;

@@ -15,20 +15,28 @@
   train pass at theta0 (hidden state carried, detached), clipped inner SGD step lr / meta_lr_factor, validation pass at theta', G =
   sum_i w_i grad val_i (w = (1-ratio)/(n-1), ..., ratio), clipped, plain SGD outer step.  Tasks are sharded over ranks like the ASR
   loop with ONE all-reduce of the flat G.  **Parity unpinned** against the reference loop; pinned against the oracle restatement.
+* `LMEngine.evaluate`, `evaluate`, `evaluate_test`: validation / test loss of a batchified stream and the losses by language
+  transition (lm/test.py:189-368), windows chunked into one recurrent call, sums in fp64 on the device (DESIGN.md section 18);
+  `LMMetaTrainer.train(valid_interval=...)` evaluates periodically, anneals lr, stops early and saves.
+* `Dictionary`, `Corpus`, `batchify`: lm/util/data.py:69-195; `save_lm_checkpoint`: the file lmscore.LM loads for rescoring.
 No CPU fallback: without a GPU / the built library every compute call raises.
 """
 import ctypes
 import math
+import os
+import random
 import time
 
 import torch
 import torch.nn as nn
 
 from . import _lib, dist as mdist
+from .data import is_contain_chinese_word
 from .engine import ParamLayout
 
 check = _lib.check
 ACCUM = 2
+MAX_KEYS = 4096        # MTL_NLL_MAX_KEYS of include/mtl_hip.h
 
 
 
@@ -224,9 +232,89 @@ class LMEngine:
         self.check_handoff()          # the caller ranks hypotheses by these values
         return seq.clone()
 
-    def _recurrent(self, theta, x, hidden, dropout_p):
+    def evaluate(self, theta, source, bptt, lang=None, eos_id=None, chunk_windows=None, rows=False):
+        """Evaluation loss of a batchified stream (lm/main_meta_transfer.py:214-267, lm/test.py:189-241 `evaluate`; with `lang` the
+        language-transition sums of lm/test.py:243-368 `evaluate_test`).  source (S, B) int64 on the device.  Evaluation mode (no dropout,
+        whatever model.training says; no random number is drawn), hidden state zero at the start and carried from window to window.
+        Windows start at i = 0, bptt, ... < S - 1; window w has T_w = min(bptt, S - 1 - i) steps and the targets source[i+1 : i+1+T_w];
+        loss = sum_w T_w mean_w / S with mean_w the mean row NLL of window w (the reference divides by len(data_source) = S, not by the
+        S - 1 predictions: kept).
+
+        `chunk_windows` windows at a time run as ONE call of the recurrent half (T = chunk_windows bptt; the carried state makes that
+        the same recurrence), the state is handed from chunk to chunk and a window is never split; the default keeps at most 8192 rows
+        per chunk.  Per chunk: mtl_lm_nll_fwd (no logits written), mtl_nll_key_sum over equal segments of bptt B rows for the window
+        sums and, with `lang` ((V,) uint8 on the device, 1 = a Chinese word) and `eos_id`, mtl_lm_switch_keys + mtl_nll_key_sum over
+        the four transition classes 0 zh->zh, 1 zh->en, 2 en->zh, 3 en->en (pairs that touch <eos> are skipped).  All sums are fp64 on
+        the device; ONE read-back at the end, after check_handoff().
+
+        -> dict(loss: float, combined on the host in fp64 from the window sums; window_sum (W,) float64; class_sum (4,) float64 and
+        class_count (4,) int64, or None without `lang`; row_logp (S - 1, B) fp32 on the device = -row_nll, only with rows=True).
+        Like sequence_nll it reuses forward()'s buffers: a pending backward() is invalidated."""
+        m, lib = self.m, self.lib
+        if source.dim() != 2 or int(source.shape[0]) < 2:
+            raise ValueError('source must be a batchified (S, B) stream with S >= 2')
+        if lang is not None and eos_id is None:
+            raise ValueError('evaluate(lang=...) needs eos_id: pairs that touch <eos> are not counted')
+        S, B, bptt = int(source.shape[0]), int(source.shape[1]), int(bptt)
+        if bptt < 1:
+            raise ValueError('bptt must be positive')
+        H, V, NL = m.nhid, m.ntoken, m.nlayers
+        seg, W = bptt * B, (S - 1 + bptt - 1) // bptt
+        cw = max(8192 // seg, 1) if chunk_windows is None else int(chunk_windows)
+        cw = max(1, min(cw, W, MAX_KEYS))
+        nchunk = (W + cw - 1) // cw
+        self.saved = None
+        src = self.buf('eval_src', (S, B), torch.int64)
+        src.copy_(source.detach().to(torch.int64), non_blocking=True)
+        if lang is not None:
+            if tuple(lang.shape) != (V,) or lang.dtype != torch.uint8 or lang.device != src.device:
+                raise ValueError('lang must be a (ntoken,) uint8 tensor on the device')
+            key = self.buf('eval_key', (min(cw * seg, (S - 1) * B),), torch.int32)
+        # ONE result blob: [window sums W f64 | class sums nchunk x 4 f64 | window counts W i32 | class counts nchunk x 4 i32]
+        o_cs, o_wc, o_cc = 8 * W, 8 * W + 32 * nchunk, 12 * W + 32 * nchunk
+        out = self.buf('eval_out', (o_cc + 16 * nchunk,), torch.uint8)
+        row = self.buf('eval_row', ((S - 1) * B if rows else min(cw * seg, (S - 1) * B),))
+        zero = self.buf('nll_h0', (NL, B, H))
+        zero.zero_()
+        hidden = zero if m.rnn_type == 'GRU' else (zero, zero)
+        P = theta.data_ptr()
+        for c in range(nchunk):
+            i0 = c * cw * bptt
+            T = min(cw * bptt, S - 1 - i0)
+            R, nw = T * B, min(cw, W - c * cw)
+            rec = self._recurrent(theta, src[i0:i0 + T], hidden, 0.0, for_backward=False)
+            hidden = rec['hn'].clone() if rec['cn'] is None else (rec['hn'].clone(), rec['cn'].clone())
+            ids_p, tgt_p = src.data_ptr() + 8 * i0 * B, src.data_ptr() + 8 * (i0 + 1) * B
+            row_p = row.data_ptr() + (4 * i0 * B if rows else 0)
+            need = int(lib.mtl_lm_nll_workspace(R, V))
+            ws = self.ws if need <= self.ws.numel() * 4 else self.buf('nll_ws', ((need + 3) // 4,))
+            check(lib.mtl_lm_nll_fwd(self.stream, rec['last'].data_ptr(), H, P + 4 * self.off('decoder.weight'), P + 4 * self.off('decoder.bias'),
+                                     tgt_p, R, H, V, B, row_p, None, ws.data_ptr(), ws.numel() * 4), 'mtl_lm_nll_fwd')
+            kws = self.buf('eval_kws', ((int(lib.mtl_nll_key_sum_workspace(R, max(nw, 4))) + 7) // 8,), torch.float64)
+            check(lib.mtl_nll_key_sum(self.stream, row_p, None, seg, R, nw, out.data_ptr() + 8 * c * cw, out.data_ptr() + o_wc + 4 * c * cw,
+                                      kws.data_ptr(), kws.numel() * 8), 'mtl_nll_key_sum (windows)')
+            if lang is not None:
+                check(lib.mtl_lm_switch_keys(self.stream, ids_p, tgt_p, lang.data_ptr(), int(eos_id), R, V, key.data_ptr()), 'mtl_lm_switch_keys')
+                check(lib.mtl_nll_key_sum(self.stream, row_p, key.data_ptr(), 1, R, 4, out.data_ptr() + o_cs + 32 * c,
+                                          out.data_ptr() + o_cc + 16 * c, kws.data_ptr(), kws.numel() * 8), 'mtl_nll_key_sum (classes)')
+        self.saved = None
+        if rows:
+            check(lib.mtl_scale(self.stream, row.data_ptr(), -1.0, None, (S - 1) * B), 'mtl_scale')
+        self.check_handoff()
+        host = out.cpu().numpy()                                   # the one read-back
+        window_sum = host[:o_cs].view('<f8').copy()
+        res = dict(loss=float(window_sum.sum(dtype='f8') / (B * S)), window_sum=window_sum, class_sum=None, class_count=None)
+        if lang is not None:
+            res['class_sum'] = host[o_cs:o_wc].view('<f8').reshape(nchunk, 4).sum(axis=0)
+            res['class_count'] = host[o_cc:].view('<i4').reshape(nchunk, 4).astype('i8').sum(axis=0)
+        if rows:
+            res['row_logp'] = row.view(S - 1, B).clone()
+        return res
+
+    def _recurrent(self, theta, x, hidden, dropout_p, for_backward=True):
         """the recurrent half of forward(): embedding (+ dropout) and the LSTM stack over x (T, B) from `hidden` -> dict with the top
-        layer's (dropped) output `last` (T B, H) and what backward() needs"""
+        layer's (dropped) output `last` (T B, H) and what backward() needs (for_backward=False: without the occurrence chains of the
+        embedding scatter-add, which only backward() reads)"""
         m, lib, st = self.m, self.lib, self.stream
         T, B = int(x.shape[0]), int(x.shape[1])
         R, H, E, V, NL = T * B, m.nhid, m.ninp, m.ntoken, m.nlayers
@@ -238,8 +326,10 @@ class LMEngine:
         xh = x.detach().to(torch.int64).contiguous()
         ids = self.buf('ids', (R,), torch.int64)
         ids.copy_(xh.reshape(-1), non_blocking=True)
-        chains = self.buf('chains', (2, R), torch.int32)
-        chains.copy_(self._chains(xh), non_blocking=True)
+        chains = None
+        if for_backward:
+            chains = self.buf('chains', (2, R), torch.int32)
+            chains.copy_(self._chains(xh), non_blocking=True)
         sc = 1.0 / (1.0 - dropout_p) if dropout_p > 0 else 1.0
         seed = self.buf('seed', (1,), torch.int64)
         if dropout_p > 0:
@@ -566,13 +656,33 @@ class LMMetaTrainer:
         batch_loss = sum(w[tid] * float(v) for v, tid in zip(val_losses, task_ids))
         return batch_loss, [float(t) for t in tr_losses]
 
-    def train(self, dataset, start_it, num_it, log_interval=200):
-        """loop of lm/main_meta_transfer.py:277-411 without the periodic evaluation: per iteration every task's train batch
-        `sample(i, it)`, the shared validation batch `sample(-1, it)`; tasks sharded over ranks"""
+    def train(self, dataset, start_it, num_it, log_interval=200, valid_interval=None, val_data=None, test_data=None, save_path=None,
+              dictionary=None, eval_bptt=None, patience=5):
+        """loop of lm/main_meta_transfer.py:277-411: per iteration every task's train batch `sample(i, it)`, the shared validation
+        batch `sample(-1, it)`; tasks sharded over ranks.
+
+        valid_interval=None: no periodic evaluation, returns None.  With valid_interval (:370-411): at it % valid_interval == 0 and
+        it > 0 the loss of `val_data` (and of `test_data` if given; batchified (S, B) streams, windows of eval_bptt or the dataset's
+        bptt) is evaluated and printed, `anneal_step` decides -- a first or better validation loss is saved to `save_path` with
+        save_lm_checkpoint(model, dictionary, save_path), any other divides self.lr by 4 -- and the loop stops after `patience`
+        evaluations without improvement in a row.  The logged running loss is then reset only at an evaluation and divided by
+        it % valid_interval (valid_interval when that is 0), as the reference does.  An evaluation changes nothing the training
+        reads (self.hidden, model.training, no random numbers).  Under several ranks every rank evaluates the same data -- the
+        replicas are identical, so is the decision -- and rank 0 writes the file and prints.
+        -> dict(best_val_loss, evaluations [(it, val, test or None, lr after the decision)], stopped_early)"""
         rank, world = mdist.rank(), mdist.world_size()
         n = len(dataset.task_list)
         mine = mdist.shard_tasks(n, rank, world)
         dev = self.model.flat_parameters.device
+        if valid_interval is not None:
+            if int(valid_interval) < 1 or val_data is None:
+                raise ValueError('train(valid_interval=...) needs a positive interval and val_data')
+            if save_path is not None and dictionary is None:
+                raise ValueError('train(save_path=...) needs the dictionary the checkpoint carries')
+            val_data = val_data.to(dev)
+            test_data = test_data.to(dev) if test_data is not None else None
+        bptt = eval_bptt or dataset.bptt
+        best, counter, evaluations, stopped = None, 0, [], False
         total, t0 = 0.0, time.time()
         self.model.train()
         for it in range(start_it, num_it):
@@ -581,7 +691,134 @@ class LMMetaTrainer:
             loss, _ = self.run_iteration([(x.to(dev), y.to(dev)) for x, y in batches], (vx.to(dev), vy.to(dev)), n, mine)
             total += mdist.allreduce_scalars([loss], dev)[0]
             if it % log_interval == 0 and it > 0 and rank == 0:
-                cur = total / log_interval
+                cur = total / (log_interval if valid_interval is None else (it % valid_interval or valid_interval))
                 print('| it {:3d} | lr {:02.2f} | ms/batch {:5.2f} | word_loss {:5.2f} | avg ppl {:8.2f}'.format(
                     it, self.lr, (time.time() - t0) * 1000 / log_interval, cur, math.exp(min(cur, 50.0))))
-                total, t0 = 0.0, time.time()
+                t0 = time.time()
+                if valid_interval is None:
+                    total = 0.0
+            if valid_interval is None or it % valid_interval != 0 or it == 0:
+                continue
+            val = evaluate(self.model, val_data, bptt)
+            test = evaluate(self.model, test_data, bptt) if test_data is not None else None
+            if rank == 0:
+                print('it {} | val loss {:5f} | ppl {:5f}'.format(it, val, math.exp(min(val, 50.0))))
+                if test is not None:
+                    print('it {} | test loss {:5f} | ppl {:5f}'.format(it, test, math.exp(min(test, 50.0))))
+            best, counter, self.lr, save, stop = anneal_step(best, counter, self.lr, val, patience)
+            if save and save_path is not None and rank == 0:
+                save_lm_checkpoint(self.model, dictionary, save_path)
+            evaluations.append((it, val, test, self.lr))
+            total = 0.0
+            if stop:
+                stopped = True
+                break
+        if valid_interval is None:
+            return None
+        return dict(best_val_loss=best, evaluations=evaluations, stopped_early=stopped)
+
+
+def anneal_step(best, counter, lr, val, patience=5):
+    """The decision after a validation (lm/main_meta_transfer.py:397-408): `not best or val < best` -- a first value, a better one,
+    and (the reference's quirk, kept) any value after a best of exactly 0 -- is saved and resets the counter; anything else divides
+    lr by 4 and counts.  -> (best, counter, lr, save, stop) with stop = counter == patience."""
+    if not best or val < best:
+        return val, 0, lr, True, False
+    counter += 1
+    return best, counter, lr / 4.0, False, counter == patience
+
+
+class Dictionary(object):
+    """lm/util/data.py:69-81"""
+
+    def __init__(self):
+        self.word2idx = {}
+        self.idx2word = {}
+
+    def add_word(self, word):
+        if word not in self.word2idx:
+            self.idx2word[len(self.idx2word)] = word
+            self.word2idx[word] = len(self.idx2word) - 1
+        return self.word2idx[word]
+
+    def __len__(self):
+        return len(self.idx2word)
+
+
+class Corpus(object):
+    """lm/util/data.py:83-195: `.train`, `.valid`, `.test` int64 id streams and `.train_lang`, ... (1 = a word that contains a Chinese
+    character, else 0).  '<oov>' is added first; per line strip().lower(), ONE replace('  ', ' '), split(), '<eos>' appended.  Only the
+    training file adds words: unknown words of the other two map to '<oov>'.  A `dictionary` passed in is extended (the reference
+    chains its corpora this way)."""
+
+    def __init__(self, train_path, valid_path=None, test_path=None, dictionary=None, seed=1000):
+        random.seed(seed)
+        self.dictionary = Dictionary() if dictionary is None else dictionary
+        self.train, self.train_lang = self.tokenize(train_path, True)
+        if valid_path is not None:
+            self.valid, self.valid_lang = self.tokenize(valid_path, False)
+        if test_path is not None:
+            self.test, self.test_lang = self.tokenize(test_path, False)
+
+    def tokenize(self, path, save, randomize=False):
+        assert os.path.exists(path)
+        d = self.dictionary
+        d.add_word('<oov>')
+        ids, langs = [], []
+        with open(path, 'r') as f:
+            lines = [line.strip().lower().replace('  ', ' ').split() + ['<eos>'] for line in f]
+        if save:
+            for words in lines:
+                for word in words:
+                    d.add_word(word)
+        oov = d.word2idx['<oov>']
+        for words in lines:
+            for word in words:
+                ids.append(d.word2idx.get(word, oov))
+                langs.append(1 if is_contain_chinese_word(word) else 0)
+        return torch.tensor(ids, dtype=torch.int64), torch.tensor(langs, dtype=torch.int64)
+
+
+def batchify(data, bsz):
+    """lm/util/data.py:25-34 as a free function: (N,) -> (N // bsz, bsz), column b = the b-th contiguous part (on data's device)"""
+    nbatch = data.size(0) // bsz
+    return data.narrow(0, 0, nbatch * bsz).view(bsz, -1).t().contiguous()
+
+
+def language_table(dictionary, ntoken, device):
+    """(ntoken,) uint8: 1 where the dictionary's word contains a Chinese character (mtl_lm_switch_keys' `lang`)"""
+    lang = torch.zeros(ntoken, dtype=torch.uint8)
+    for i, w in dictionary.idx2word.items():
+        if i < ntoken and is_contain_chinese_word(w):
+            lang[i] = 1
+    return lang.to(device)
+
+
+def evaluate(model, data_source, bptt=35):
+    """lm/main_meta_transfer.py:214-267 -> the loss (LMEngine.evaluate; data_source: a batchified (S, B) stream)"""
+    eng = model._need_engine()
+    return eng.evaluate(model.flat_parameters, data_source.to(model.flat_parameters.device), bptt)['loss']
+
+
+def evaluate_test(model, data_source, dictionary, bptt=35):
+    """lm/test.py:243-368 with type_evaluation='test' -> the reference's 6-tuple in its order: (loss, zh->zh mean, zh->en mean,
+    en->zh mean, en->en mean, switch-point mean = (zh->en sum + en->zh sum) / (both counts)).  The reference NAMES the second entry
+    `en_en`, but its source_lang is True for a Chinese word: the first class is zh->zh.  Deviations: an empty class gives nan (the
+    reference raises ZeroDivisionError), and any batch width works (the reference's squeeze() works for a width of 1 only)."""
+    eng = model._need_engine()
+    dev = model.flat_parameters.device
+    res = eng.evaluate(model.flat_parameters, data_source.to(dev), bptt, lang=language_table(dictionary, model.ntoken, dev),
+                       eos_id=dictionary.word2idx['<eos>'])
+    s, c = [float(v) for v in res['class_sum']], [int(v) for v in res['class_count']]
+    mean = lambda a, b: a / b if b else float('nan')
+    return (res['loss'], mean(s[0], c[0]), mean(s[1], c[1]), mean(s[2], c[2]), mean(s[3], c[3]), mean(s[1] + s[2], c[1] + c[2]))
+
+
+def save_lm_checkpoint(model, dictionary, path):
+    """The dict of lm/convert.py:431-446, which lmscore.LM (and the reference's utils/lm.py LM) reads: model_state_dict (host copies;
+    a tied model keeps both encoder.weight and decoder.weight), word2idx, idx2word, ntoken, ninp, nhid, nlayers, dropout and
+    tie_weights -- the model's real flag, where the reference hard-codes True -- plus rnn_type."""
+    state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    torch.save(dict(model_state_dict=state, word2idx=dictionary.word2idx, idx2word=dictionary.idx2word,
+                    ntoken=int(model.encoder.weight.size(0)), ninp=int(model.encoder.weight.size(1)), nhid=model.nhid,
+                    nlayers=model.nlayers, dropout=model.drop.p, tie_weights=bool(model.tie_weights), rnn_type=model.rnn_type), path)
