@@ -3,9 +3,12 @@
 Import as `mtl_amd` (see mtl_amd.py at the repository root; the directory name carries a hyphen).
 """
 from . import _lib  # noqa: F401
-from .data import (Vocab, SyntheticTask, ManifestTaskDataset, SpectrogramDataset, BucketingSampler, AudioDataLoader, SpectrogramFrontEnd, LogFBankFrontEnd, LogFBankDataset, fbank_geometry, fbank_frames, mel_filterbank, mel_filterbank_sparse, NoiseInjection, TempoGainAugment, load_randomly_augmented_audio, tempo_gain, tempo_gain_tables, resample, resample_plan, resample_taps, resample_tables, load_wav_pcm16_rate,
-                   wsola_geometry, load_vocab, load_wav_pcm16, pack_waveforms, synthetic_vocab,  # noqa: F401
+from .data import (Vocab, SyntheticTask, ManifestTaskDataset, SpectrogramDataset, BucketingSampler, AudioDataLoader, LogFBankDataset,  # noqa: F401
+                   load_wav_pcm16_rate, load_vocab, load_wav_pcm16, synthetic_vocab,
                    synth_batch, is_chinese_char, is_contain_chinese_word, get_word_segments_per_language)
+from .frontend import (SpectrogramFrontEnd, LogFBankFrontEnd, fbank_geometry, fbank_frames, mel_filterbank, mel_filterbank_sparse,  # noqa: F401
+                       NoiseInjection, TempoGainAugment, load_randomly_augmented_audio, tempo_gain, tempo_gain_tables, resample, resample_plan,
+                       resample_taps, resample_tables, wsola_geometry, pack_waveforms)
 from .functions import (init_transformer_model, save_meta_model, load_meta_model, save_joint_model, load_joint_model,  # noqa: F401
                         post_process, compute_num_params)
 from .discriminator import (Discriminator, init_discriminator_model, save_discriminator, load_discriminator,  # noqa: F401

@@ -1,4 +1,5 @@
-"""Utterances per second of the two ways from waveforms in host memory to a padded input batch on the device:
+"""Utterances per second of the two ways from waveforms in host memory to a padded input batch on the device (the
+front-end classes and their `batch` are in frontend.py):
 
   (a) per utterance: K x `SpectrogramFrontEnd.__call__(y).cpu()`, `collate` on the host, `.to(device)`   (device_batches=False)
   (b) batched:       one `SpectrogramFrontEnd.batch(waves)`                                              (device_batches=True)
@@ -602,7 +603,9 @@ def logfbank_leg(a, mtl_amd, _lib, fe, waves, labels):
 
     # device time of the launches alone (operands on the device): the new kernel, and the spectrogram's on the same samples
     lib = _lib.lib()
-    flat, offsets, frames, tmax = fb._pack(waves, None)
+    flat, offsets = np.concatenate(waves), np.concatenate([[0], np.cumsum([len(y) for y in waves])]).astype(np.int64)
+    frames = mtl_amd.fbank_frames([len(y) for y in waves], fe.sample_rate).astype(np.int32)
+    tmax = int(frames.max())
     d_wav, d_off = torch.from_numpy(flat).to(dev), torch.from_numpy(offsets).to(dev)
     out = torch.empty(K, 1, 80, tmax, device=dev)
     ws_bytes = lib.mtl_fbank_batch_workspace(K)
