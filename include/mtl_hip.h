@@ -119,6 +119,16 @@ int mtl_conv0_relu_fwd_tb(void* stream, const float* x, const float* w, const fl
                           int tasks, long sX, long sW, long sBias, long sAmax);
 int mtl_conv0_wgrad_tb(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int tasks,
                        long sX, long sDw, long sDb);
+/* the same four calls with C output channels: w (C,1,3,3), y / dy (B,T,F,C); C = 64 (vgg_cnn: exactly the calls above) or 32 (large_cnn,
+ * models/asr/transformer.py:60-72).  Same workspace. */
+int mtl_conv0c_relu_fwd(void* stream, const float* x_ref, const float* w, const float* bias, float* y, int B, int T, int F, int C,
+                        float* amax_y);
+int mtl_conv0c_wgrad(void* stream, const float* x_ref, const float* dy, float* dw /*accum*/, float* db /*accum*/, float* workspace, int B,
+                     int T, int F, int C);
+int mtl_conv0c_relu_fwd_tb(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, int C,
+                           float* amax_y, int tasks, long sX, long sW, long sBias, long sAmax);
+int mtl_conv0c_wgrad_tb(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int C,
+                        int tasks, long sX, long sDw, long sDb);
 /* column sums of `tasks` contiguous row blocks (rows x cols each) in one launch pair; workspace: tasks x mtl_colsum_workspace(rows, cols)
  * bytes (+ 16 per task); cols = 4 x 2^j <= 256, 16-byte aligned X */
 int mtl_colsum_accum_tb(void* stream, const float* X, long rows, int cols, float* out, float* workspace, float* amax, int tasks, long sOut,
@@ -139,7 +149,9 @@ int mtl_conv3x3_dgrad(void* stream, const float* dy, const unsigned char* argmax
 /* Split-bf16 ("x3") variants of the three calls above: identical semantics and fp32-class error, computed with six
  * v_mfma_f32_32x32x16_bf16 per 16-deep step on exact 3-way bf16 splits of both operands (2.67x the fp32 MFMA roof).
  * w3_fwd / w3_dgrad: bf16 [3][K-tile][rows][32] buffers (3 * 9*Cin*Cout * 2 bytes each) from mtl_conv3x3_wprep_x3; the four
- * 16-byte chunks of a row are stored at chunk ^ ((row >> 2) & 3) (the LDS image the kernels DMA with global_load_lds). */
+ * 16-byte chunks of a row are stored at chunk ^ ((row >> 2) & 3) (the LDS image the kernels DMA with global_load_lds).
+ * Shapes: Cin and Cout multiples of 64, and -- on the x3 calls only, single-task and _tb, weight gradients included -- the two narrow
+ * layers of the large_cnn front-end, (Cin, Cout) = (32, 32) and (32, 64) (csrc/mtl_conv_narrow.hip).  Any other shape: MTL_EINVAL. */
 int mtl_conv3x3_wprep_x3(void* stream, const float* w_ref, void* w3_fwd, void* w3_dgrad, int Cout, int Cin);
 int mtl_conv3x3_relu_fwd_x3(void* stream, const float* x, const void* w3_fwd, const float* bias, float* y, int B, int T, int F,
                             int Cin, int Cout);

@@ -1,7 +1,8 @@
 """The VGG front-end of a pass and the encoder's input Linear: everything between the input batch and e0, and between de0 and
 conv0's weight gradient, as calls into libmtl_hip.so.  conv0 (1 -> 64), the three 3 x 3 layers of LAYERS, the input Linear (5120 ->
-512) on the permuted weight.  One table row per 3 x 3 layer, one adapter per precision mode (which call, which argument order), one
-walker per direction:
+512) on the permuted weight -- or, for a model built with feat_extractor='large_cnn', the same shape at half the width: conv0 (1 -> 32),
+LAYERS_LARGE, 2560 inputs (STACKS; layers_for() tells the two apart by conv0's channel count).  One table row per 3 x 3 layer, one
+adapter per precision mode (which call, which argument order), one walker per direction:
   * 'f32' issues single-task calls, task by task -- layer by layer when the tasks bring frame counts of their own (`widths`), a
     layer's tails being cleared for all tasks before the next layer reads them;
   * 'x3' and 'h2' issue ONE `_tb` launch per layer for the samples of all tasks when the pass carries several tasks or `widths` (a
@@ -39,11 +40,29 @@ def _layer(i, idx, cin, cout, pool, lvl, x, y, am, dy, dx, own_bias=False):
 LAYERS = (_layer(0, 2, 64, 64, True, 0, 'y1', 'p1', 'am1', '_dp1', '_dy1'),
           _layer(1, 5, 64, 128, False, 1, 'p1', 'y5', None, '_dy5', '_dp1'),
           _layer(2, 7, 128, 128, True, 1, 'y5', 'p2', 'am2', '_dp2', '_dy5', own_bias=True))
+# the reference's large_cnn (models/asr/transformer.py:60-72): the same arena names -- oracle/branches.py reads them, channel-agnostic
+LAYERS_LARGE = (_layer(0, 2, 32, 32, True, 0, 'y1', 'p1', 'am1', '_dp1', '_dy1'),
+                _layer(1, 5, 32, 64, False, 1, 'p1', 'y5', None, '_dy5', '_dp1'),
+                _layer(2, 7, 64, 64, True, 1, 'y5', 'p2', 'am2', '_dp2', '_dy5', own_bias=True))
+STACKS = {'vgg_cnn': LAYERS, 'large_cnn': LAYERS_LARGE}
+
+
+def layers_for(layout):
+    """the layer table of a model, by the output channels of its conv0 (ParamLayout)"""
+    c0 = layout.entries['conv.0.weight'][1][0]
+    for layers in STACKS.values():
+        if layers[0].cin == c0:
+            return layers
+    raise NotImplementedError('no convolution stack with %d channels behind conv0' % c0)
 
 
 def decide(eng, nt, widths):
-    """what the front-end of a pass runs on, read ONCE at the start of its forward from the engine's assignable attributes, kept in `saved`"""
+    """what the front-end of a pass runs on, read ONCE at the start of its forward from the engine's assignable attributes, kept in `saved`.
+    A large_cnn model runs on the exact split whatever conv_h2 / conv_x3 say: its 32-channel layers exist in that arithmetic only
+    (csrc/mtl_conv_narrow.hip), so conv_mode is 'x3', in_h2 is False and the trainer's periodic h2 census is skipped."""
     mode = 'h2' if eng.conv_h2 else ('x3' if eng.conv_x3 else 'f32')
+    if eng.conv_layers is not LAYERS:
+        mode = 'x3'
     return dict(conv_mode=mode, conv_tb=mode != 'f32' and (nt > 1 or widths is not None), in_h2=mode == 'h2' and eng.in_linear == 'h2')
 
 
@@ -58,7 +77,7 @@ class _F32:
 
     def weights(self, fr):
         """one wprep per layer and parameter set"""
-        for r in LAYERS:
+        for r in fr.layers:
             wf = fr.eng.buf(r.wf, (fr.ntw,) + self.wshape + (9, r.cin, r.cout), self.wdtype)
             wd = fr.eng.buf(r.wd, (fr.ntw,) + self.wshape + (9, r.cout, r.cin), self.wdtype)
             for t in range(fr.ntw):
@@ -104,7 +123,7 @@ class _H2:
     def weights(self, fr):
         """all three layers in one call (two launches): of ALL parameter sets when the pass reads a theta' stack"""
         spec, strides = [], []
-        for r in LAYERS:
+        for r in fr.layers:
             nb = (fr.lib.mtl_conv3x3_wprep_h2_bytes(r.cout, r.cin) + 255) // 256 * 256       # the pieces + the scale
             wf, wd = fr.eng.buf(r.wf, (fr.ntw, nb), torch.uint8), fr.eng.buf(r.wd, (fr.ntw, nb), torch.uint8)
             spec += [fr.o(r.weight), wf.data_ptr(), wd.data_ptr(), r.cout, r.cin]
@@ -154,7 +173,9 @@ class Front:
         self.wn = 1 if self.ntw > 1 else 0                                      # rows of a weight buffer from one task to the next
         self.widths, self.mode, self.tb, self.in_h2 = S['meta'].get('widths'), S['conv_mode'], S['conv_tb'], S['in_h2']
         self.tasks = (None,) if self.tb else range(self.nt)
-        self.dims = [(B,) + TF[r.lvl] + (r.cin, r.cout) for r in LAYERS]       # by Layer.i
+        self.layers = eng.conv_layers
+        self.c0, self.c_out = self.layers[0].cin, self.layers[-1].cout         # channels behind conv0 and in front of the input Linear
+        self.dims = [(B,) + TF[r.lvl] + (r.cin, r.cout) for r in self.layers]  # by Layer.i
         self.ad = _ADAPTERS[self.mode]
         self.d, self.d_in, self.Me = eng.hp.d, eng.hp.d_in, B * TF[2][0]        # (Me: encoder rows per task)
         self.wp_strides = (AMAX_STRIDE, self.d * self.d_in) if self.sP else (0, 0)      # bound / weight of the next task's parameter set
@@ -162,7 +183,7 @@ class Front:
         self.o = lambda n, t=None: P + 4 * (off(n) + (t or 0) * sP)             # task t's parameter / its gradient; None: the stack's base
         self.g = lambda n, t=None: G + 4 * (off(n) + (t or 0) * sG)
         if G is None:       # (forward: y1 first, then the bounds -- the order in which the pool has always taken them from the device)
-            eng.buf('y1', (self.nt * B, T, F, 64))
+            eng.buf('y1', (self.nt * B, T, F, self.c0))
         amax = (eng.buf('amax', (self.nt, AMAX_PER_TASK, _lib.AMAX_SLOTS)) if G is None else self.A['amax']).data_ptr()
         self.am = (lambda i, t=None: None if i is None else amax + 4 * _lib.AMAX_SLOTS * (AMAX_PER_TASK * (t or 0) + i)) if self.mode == 'h2' \
             else (lambda i, t=None: None)
@@ -198,38 +219,40 @@ class Front:
         """x -> y1 -> p1 -> y5 -> p2, and the permuted weight of the input Linear (arena)"""
         eng, nt, B, ad = self.eng, self.nt, self.B, self.ad
         Bt, (T, F) = nt * B, self.TF[0]
-        head = (self.st, self.x.data_ptr(), self.o('conv.0.weight'), self.o('conv.0.bias'), self.at('y1', None), B, T, F, self.am(0))
+        layers = self.layers
+        c0 = () if self.c0 == 64 else (self.c0,)        # (64 channels: the calls without a channel count)
+        head = (self.st, self.x.data_ptr(), self.o('conv.0.weight'), self.o('conv.0.bias'), self.at('y1', None), B, T, F, *c0, self.am(0))
         if self.mode == 'h2':
             check(self.lib.mtl_memset_zero(self.st, self.am(0), nt * AMAX_STRIDE * 4), 'mtl_memset_zero')
         if nt > 1:      # every task's samples in one launch (task = grid dimension; sX = 0: the shared validation batch), in every mode
-            check(self.lib.mtl_conv0_relu_fwd_tb(*head, nt, self.sX, self.sP, self.sP, AMAX_STRIDE), 'conv0')
+            check((self.lib.mtl_conv0c_relu_fwd_tb if c0 else self.lib.mtl_conv0_relu_fwd_tb)(*head, nt, self.sX, self.sP, self.sP, AMAX_STRIDE), 'conv0')
         else:
-            check(self.lib.mtl_conv0_relu_fwd(*head), 'conv0')
-        self.tails('y1', 0, 64)
+            check((self.lib.mtl_conv0c_relu_fwd if c0 else self.lib.mtl_conv0_relu_fwd)(*head), 'conv0')
+        self.tails('y1', 0, self.c0)
         ad.weights(self)
-        for r in LAYERS:
+        for r in layers:
             for name, dtype in ((r.y, torch.float32), (r.am, torch.uint8)):
                 if name is not None:
                     eng.buf(name, (Bt,) + self.TF[r.lvl + r.pool] + (r.cout,), dtype)
         if self.tb or self.widths is not None:      # layer by layer; what another convolution reads is cleared before it does
-            for r in LAYERS:
+            for r in layers:
                 for t in self.tasks:
                     ad.fwd(self, r, t)
-                if r is not LAYERS[-1]:
+                if r is not layers[-1]:
                     self.tails(r.y, r.lvl + r.pool, r.cout)
             if self.tb:     # the launches left out the tile rows beyond a task's frames: everything a later kernel reads there is cleared
-                self.tails('p2', 2, 128)                # (after conv7 and with the _tb launches only; the per-task path leaves these three)
-                for r in LAYERS:
+                self.tails('p2', 2, self.c_out)         # (after conv7 and with the _tb launches only; the per-task path leaves these three)
+                for r in layers:
                     if r.pool:
                         self.tails(r.am, r.lvl + 1, r.cout // 4)      # (arg-max bytes, four to a float)
         else:
             for t in range(nt):                     # task by task
-                for r in LAYERS:
+                for r in layers:
                     ad.fwd(self, r, t)
         self.census(('y1', 'p1', 'y5', 'p2'))
-        # wp_in: the input Linear's weight with its 5120 inputs in p2's (bin, channel) order; max|w| rides along; a theta' stack in one launch
+        # wp_in: the input Linear's weight with its 5120 (2560) inputs in p2's (bin, channel) order; max|w| rides along; a theta' stack in one launch
         wp = eng.buf('wp_in', (self.ntw, self.d, self.d_in))
-        check(self.lib.mtl_permute_hc_tb(self.st, self.o('encoder.input_linear.weight'), wp.data_ptr(), self.d, 128, self.TF[2][1], 0,
+        check(self.lib.mtl_permute_hc_tb(self.st, self.o('encoder.input_linear.weight'), wp.data_ptr(), self.d, self.c_out, self.TF[2][1], 0,
                                          self.am(SLOT['wp']), self.ntw, self.sP, self.d * self.d_in, AMAX_STRIDE), 'permute')
 
     def linear_fwd(self):
@@ -252,7 +275,7 @@ class Front:
         eng, st, nt, Me, d, d_in = self.eng, self.st, self.nt, self.Me, self.d, self.d_in
         (T4, F4), p2, a8 = self.TF[2], self.A['p2'], self.am(SLOT['de0'])
         dwp = eng.buf('_dwp', (nt, d, d_in))
-        eng.buf('_dp2', (nt * self.B, T4, F4, 128))
+        eng.buf('_dp2', (nt * self.B, T4, F4, self.c_out))
         if self.in_h2:
             if nt > 1:
                 check(self.lib.mtl_absmax_f32_tb(st, de0.data_ptr(), Me * d, a8, nt, Me * d, AMAX_STRIDE), 'mtl_absmax_f32')
@@ -263,7 +286,7 @@ class Front:
                                              dwp.data_ptr(), d_in, nt, Me * d, Me * d_in, d * d_in), 'mtl_gemm_h2_tn_tb')
         else:
             eng.gemm(1, 0, d, d_in, Me, de0.data_ptr(), d, p2.data_ptr(), d_in, dwp.data_ptr(), d_in, task=(Me * d, Me * d_in, d * d_in, 0, 0))
-        check(self.lib.mtl_permute_hc_tb(st, dwp.data_ptr(), self.g('encoder.input_linear.weight'), d, 128, F4, 1, None, nt, d * d_in, self.sG, 0),
+        check(self.lib.mtl_permute_hc_tb(st, dwp.data_ptr(), self.g('encoder.input_linear.weight'), d, self.c_out, F4, 1, None, nt, d * d_in, self.sG, 0),
               'permute_inv')
 
     def linear_dgrad(self, de0):
@@ -280,15 +303,16 @@ class Front:
 
     def convs_bwd(self):
         """dp2 -> the parameter gradients of conv7, conv5, conv2 and conv0"""
-        eng, lib, st, nt, B, ad = self.eng, self.lib, self.st, self.nt, self.B, self.ad
+        eng, lib, st, nt, B, ad, layers = self.eng, self.lib, self.st, self.nt, self.B, self.ad, self.layers
         T, F = self.TF[0]
-        for r in LAYERS[::-1]:
+        c0 = () if self.c0 == 64 else (self.c0,)
+        for r in layers[::-1]:
             eng.buf(r.dx, (nt * B,) + self.TF[r.lvl] + (r.cin,))
         # the bias gradients of conv5 / conv2 ride on their weight-gradient launches: always with h2 (the data-gradient epilogues also
         # deliver the next bound, so the column-sum passes over dy5 and dp1 are not needed), with the exact split in the several-task launches
         ride = self.mode == 'h2' or self.tb
         for t in self.tasks:
-            for r in LAYERS[::-1]:
+            for r in layers[::-1]:
                 To, Fo = self.TF[r.lvl + r.pool]
                 bias, own = self.g(r.bias, t), r.own_bias or not ride
                 if own and t is None:
@@ -302,9 +326,9 @@ class Front:
                 if self.tb:     # the launch left out the tile rows beyond a task's frames: bias sums, bounds and weight gradients read whole tensors
                     self.tails(r.dx, r.lvl, r.cin)
             head = (st, self.x.data_ptr() + 4 * (t or 0) * self.sX, self.at('_dy1', t), self.g('conv.0.weight', t), self.g('conv.0.bias', t),
-                    eng.scratch(lib.mtl_conv0_wgrad_workspace()), B, T, F)
+                    eng.scratch(lib.mtl_conv0_wgrad_workspace()), B, T, F, *c0)
             if t is None:
-                check(lib.mtl_conv0_wgrad_tb(*head, nt, self.sX, self.sG, self.sG), 'wgrad0_tb')
+                check((lib.mtl_conv0c_wgrad_tb if c0 else lib.mtl_conv0_wgrad_tb)(*head, nt, self.sX, self.sG, self.sG), 'wgrad0_tb')
             else:
-                check(lib.mtl_conv0_wgrad(*head), 'wgrad0')
+                check((lib.mtl_conv0c_wgrad if c0 else lib.mtl_conv0_wgrad)(*head), 'wgrad0')
         self.census(('_dp2', '_dy5', '_dp1'))

@@ -812,15 +812,18 @@ __device__ __forceinline__ void conv0_stage(const float* __restrict__ x, float* 
 
 // blockIdx.y = task of a task-batched pass (round 5): its B samples of x at + task sX floats (0: every task reads the same batch), of y
 // at + task B T F 64, its weights / bias / bound at + task sW / sBias / sAmax floats
+// CH output channels (64: vgg_cnn, 32: large_cnn): CH / 4 channel groups x 1024 / CH bin slots
+template <int CH>
 __global__ __launch_bounds__(256) void conv0_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ bias, float* __restrict__ y, int B, int T,
                                                         int F, float* __restrict__ amax_y, long sX = 0, long sW = 0, long sBias = 0,
                                                         long sAmax = 0) {
     extern __shared__ __attribute__((aligned(16))) float c0_lds[];          // [C0_NB][F + 2][8]
-    const int cg = threadIdx.x & 15, sl = threadIdx.x >> 4;  // channels 4cg..4cg+3, bin slot
+    constexpr int NCG = CH / 4, SLOTS = 256 / NCG;
+    const int cg = threadIdx.x % NCG, sl = threadIdx.x / NCG;  // channels 4cg..4cg+3, bin slot
     if (blockIdx.y) {
         x += blockIdx.y * sX;
-        y += (long)blockIdx.y * B * T * F * 64;
+        y += (long)blockIdx.y * B * T * F * CH;
         w += blockIdx.y * sW;
         bias += blockIdx.y * sBias;
         if (amax_y) amax_y += blockIdx.y * sAmax;
@@ -847,14 +850,14 @@ __global__ __launch_bounds__(256) void conv0_fwd_kernel(const float* __restrict_
         const int bA = g0 / ntb, tA = (g0 - bA * ntb) * C0_TB;             // the two tiles' (utterance, first frame): uniform
         const int bB = (g0 + 1) / ntb, tB = (g0 + 1 - bB * ntb) * C0_TB;
         const int s_end = (g0 + 1 < ntiles ? 2 : 1) * F;
-        for (int s = sl; s < s_end; s += 16) {
+        for (int s = sl; s < s_end; s += SLOTS) {
             const int nb = s >= F ? 1 : 0, f = s - nb * F;   // (C0_NB == 2)
             const int b = nb ? bB : bA, t0 = nb ? tB : tA;
             const float* r = c0_lds + (nb * rows + f) * C0_ROW;           // patch row of bin f - 1
             C0Row xr[3];
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh) xr[kh].load(r + kh * C0_ROW);
-            float* yp = y + (((long)b * T + t0) * F + f) * 64 + cg * 4;
+            float* yp = y + (((long)b * T + t0) * F + f) * CH + cg * 4;
 #pragma unroll
             for (int tt = 0; tt < C0_TB; ++tt) {
                 f32x2 a01 = b01, a23 = b23;
@@ -871,7 +874,7 @@ __global__ __launch_bounds__(256) void conv0_fwd_kernel(const float* __restrict_
                 if (t0 + tt < T) {
                     mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(a01, a23));
                     const f32x4_t out = {a01.x, a01.y, a23.x, a23.y};
-                    __builtin_nontemporal_store(out, reinterpret_cast<f32x4_t*>(yp + (long)tt * F * 64));   // streamed: read next by another kernel
+                    __builtin_nontemporal_store(out, reinterpret_cast<f32x4_t*>(yp + (long)tt * F * CH));   // streamed: read next by another kernel
                 }
             }
         }
@@ -885,17 +888,19 @@ __global__ __launch_bounds__(256) void conv0_fwd_kernel(const float* __restrict_
         if (threadIdx.x == 0 && cand > seen) atomicMax(reinterpret_cast<unsigned*>(slot), __float_as_uint(cand));
     }
 }
-// dw0[c][tap] = sum_pix x[pix+tap]*dy[pix][c], db0[c] = sum_pix dy[pix][c]: per-block partials [blk][64][10].  Same tiling as the
+// dw0[c][tap] = sum_pix x[pix+tap]*dy[pix][c], db0[c] = sum_pix dy[pix][c]: per-block partials [blk][CH][10].  Same tiling as the
 // forward kernel; a thread keeps the 4 channels x (9 taps + bias) sums of its bin slot as v_pk_fma_f32 pairs.
-// blockIdx.y = task (see conv0_fwd_kernel): x at + task sX, dy at + task B T F 64, its partial rows behind the previous tasks'
+// blockIdx.y = task (see conv0_fwd_kernel): x at + task sX, dy at + task B T F CH, its partial rows behind the previous tasks'
+template <int CH>
 __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           float* __restrict__ part, int B, int T, int F, long sX = 0) {
-    extern __shared__ __attribute__((aligned(16))) float c0_lds[];          // [C0_NB][F + 2][8], re-used for the final [16][64][10]
-    const int cg = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    extern __shared__ __attribute__((aligned(16))) float c0_lds[];          // [C0_NB][F + 2][8], re-used for the final [SLOTS][CH][10]
+    constexpr int NCG = CH / 4, SLOTS = 256 / NCG, PART = CH * 10;
+    const int cg = threadIdx.x % NCG, sl = threadIdx.x / NCG;
     if (blockIdx.y) {
         x += blockIdx.y * sX;
-        dy += (long)blockIdx.y * B * T * F * 64;
-        part += (long)blockIdx.y * gridDim.x * 640;
+        dy += (long)blockIdx.y * B * T * F * CH;
+        part += (long)blockIdx.y * gridDim.x * PART;
     }
     f32x2 a01[10], a23[10];
 #pragma unroll
@@ -910,14 +915,14 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restric
         const int bA = g0 / ntb, tA = (g0 - bA * ntb) * C0_TB;             // the two tiles' (utterance, first frame): uniform
         const int bB = (g0 + 1) / ntb, tB = (g0 + 1 - bB * ntb) * C0_TB;
         const int s_end = (g0 + 1 < ntiles ? 2 : 1) * F;
-        for (int s = sl; s < s_end; s += 16) {
+        for (int s = sl; s < s_end; s += SLOTS) {
             const int nb = s >= F ? 1 : 0, f = s - nb * F;   // (C0_NB == 2)
             const int b = nb ? bB : bA, t0 = nb ? tB : tA;
-            const float* dp = dy + (((long)b * T + t0) * F + f) * 64 + cg * 4;
+            const float* dp = dy + (((long)b * T + t0) * F + f) * CH + cg * 4;
             f32x4_t d[C0_TB];
 #pragma unroll
             for (int tt = 0; tt < C0_TB; ++tt)               // the four 16-byte loads of the stream are issued together
-                d[tt] = (t0 + tt < T) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(dp + (long)tt * F * 64))
+                d[tt] = (t0 + tt < T) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(dp + (long)tt * F * CH))
                                       : f32x4_t{0.f, 0.f, 0.f, 0.f};
             const float* r = c0_lds + (nb * rows + f) * C0_ROW;
             C0Row xr[3];
@@ -939,34 +944,34 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restric
         }
     }
     __syncthreads();
-    float* sh = c0_lds;                                      // [16 slots][64 channels][10]
+    float* sh = c0_lds;                                      // [SLOTS][CH channels][10]
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
-        sh[(sl * 64 + cg * 4 + 0) * 10 + k] = a01[k].x;
-        sh[(sl * 64 + cg * 4 + 1) * 10 + k] = a01[k].y;
-        sh[(sl * 64 + cg * 4 + 2) * 10 + k] = a23[k].x;
-        sh[(sl * 64 + cg * 4 + 3) * 10 + k] = a23[k].y;
+        sh[(sl * CH + cg * 4 + 0) * 10 + k] = a01[k].x;
+        sh[(sl * CH + cg * 4 + 1) * 10 + k] = a01[k].y;
+        sh[(sl * CH + cg * 4 + 2) * 10 + k] = a23[k].x;
+        sh[(sl * CH + cg * 4 + 3) * 10 + k] = a23[k].y;
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 640; e += 256) {
+    for (int e = threadIdx.x; e < PART; e += 256) {
         float t = 0.f;
-        for (int p = 0; p < 16; ++p) t += sh[p * 640 + e];
-        part[(long)blockIdx.x * 640 + e] = t;
+        for (int p = 0; p < SLOTS; ++p) t += sh[p * PART + e];
+        part[(long)blockIdx.x * PART + e] = t;
     }
 }
 // one wave per output element: lanes stride the per-block partials, fixed-order shuffle tree
 __global__ __launch_bounds__(256) void conv0_wgrad_final_kernel(const float* __restrict__ part, int nblk, float* __restrict__ dw,
-                                                                float* __restrict__ db, long sDw = 0, long sDb = 0) {
+                                                                float* __restrict__ db, int PART, long sDw = 0, long sDb = 0) {
     if (blockIdx.y) {
-        part += (long)blockIdx.y * nblk * 640;
+        part += (long)blockIdx.y * nblk * PART;
         dw += blockIdx.y * sDw;
         db += blockIdx.y * sDb;
     }
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (e >= 640) return;
+    if (e >= PART) return;
     float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(long)b * 640 + e];
+    for (int b = lane; b < nblk; b += 64) s += part[(long)b * PART + e];
     s = wave_sum(s);
     if (lane == 0) {
         const int c = e / 10, k = e % 10;
@@ -1553,56 +1558,74 @@ int mtl_colsum_accum_tb(void* stream, const float* X, long rows, int cols, float
     return MTL_OK;
 }
 
-int mtl_conv0_relu_fwd(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, float* amax_y) {
-    if (!x || !w || !bias || !y) return MTL_EINVAL;
+// conv0 with C output channels (64: vgg_cnn, 32: large_cnn); tasks = 1 and zero strides: the single-task launch
+static int conv0_fwd(hipStream_t s, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, int C, float* amax_y,
+                     int tasks, long sX, long sW, long sBias, long sAmax) {
+    if (!x || !w || !bias || !y || tasks < 1 || tasks > 65535 || (C != 64 && C != 32)) return MTL_EINVAL;
     const long lds = (long)C0_NB * (F + 2) * C0_ROW * 4;
     if (B <= 0 || T <= 0 || F <= 0 || lds > 64 * 1024) return MTL_EINVAL;
     const long tiles = (long)B * ((T + C0_TB - 1) / C0_TB);
-    hipLaunchKernelGGL(conv0_fwd_kernel, dim3((unsigned)std::min<long>((tiles + C0_NB - 1) / C0_NB, 4096)), dim3(256), (size_t)lds,
-                       as_stream(stream), x, w, bias, y, B, T, F, amax_y);
+    const dim3 grid((unsigned)std::min<long>((tiles + C0_NB - 1) / C0_NB, 4096), tasks);
+    if (C == 64)
+        hipLaunchKernelGGL(conv0_fwd_kernel<64>, grid, dim3(256), (size_t)lds, s, x, w, bias, y, B, T, F, amax_y, sX, sW, sBias, sAmax);
+    else
+        hipLaunchKernelGGL(conv0_fwd_kernel<32>, grid, dim3(256), (size_t)lds, s, x, w, bias, y, B, T, F, amax_y, sX, sW, sBias, sAmax);
     MTL_CHECK_LAUNCH();
     return MTL_OK;
+}
+
+int mtl_conv0_relu_fwd(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, float* amax_y) {
+    return conv0_fwd(as_stream(stream), x, w, bias, y, B, T, F, 64, amax_y, 1, 0, 0, 0, 0);
 }
 
 int mtl_conv0_relu_fwd_tb(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, float* amax_y,
                           int tasks, long sX, long sW, long sBias, long sAmax) {
-    if (!x || !w || !bias || !y || tasks < 1 || tasks > 65535) return MTL_EINVAL;
-    const long lds = (long)C0_NB * (F + 2) * C0_ROW * 4;
-    if (B <= 0 || T <= 0 || F <= 0 || lds > 64 * 1024) return MTL_EINVAL;
-    const long tiles = (long)B * ((T + C0_TB - 1) / C0_TB);
-    hipLaunchKernelGGL(conv0_fwd_kernel, dim3((unsigned)std::min<long>((tiles + C0_NB - 1) / C0_NB, 4096), tasks), dim3(256), (size_t)lds,
-                       as_stream(stream), x, w, bias, y, B, T, F, amax_y, sX, sW, sBias, sAmax);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
+    return conv0_fwd(as_stream(stream), x, w, bias, y, B, T, F, 64, amax_y, tasks, sX, sW, sBias, sAmax);
+}
+
+int mtl_conv0c_relu_fwd(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, int C, float* amax_y) {
+    return conv0_fwd(as_stream(stream), x, w, bias, y, B, T, F, C, amax_y, 1, 0, 0, 0, 0);
+}
+
+int mtl_conv0c_relu_fwd_tb(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int T, int F, int C,
+                           float* amax_y, int tasks, long sX, long sW, long sBias, long sAmax) {
+    return conv0_fwd(as_stream(stream), x, w, bias, y, B, T, F, C, amax_y, tasks, sX, sW, sBias, sAmax);
 }
 
 long mtl_conv0_wgrad_workspace(void) { return 1024L * 640 * 4; }
 
-int mtl_conv0_wgrad_tb(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int tasks,
-                       long sX, long sDw, long sDb) {
-    if (!x || !dy || !dw || !db || !workspace || tasks < 1 || tasks > 256) return MTL_EINVAL;
+static int conv0_wgrad(hipStream_t s, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int C,
+                       int tasks, long sX, long sDw, long sDb) {
+    if (!x || !dy || !dw || !db || !workspace || tasks < 1 || tasks > 256 || (C != 64 && C != 32)) return MTL_EINVAL;
     const long lds = std::max<long>((long)C0_NB * (F + 2) * C0_ROW * 4, 16L * 640 * 4);
     if (B <= 0 || T <= 0 || F <= 0 || lds > 64 * 1024) return MTL_EINVAL;
     const long tiles = (long)B * ((T + C0_TB - 1) / C0_TB);
     const int nb = (int)std::min<long>((tiles + C0_NB - 1) / C0_NB, 1024 / tasks);      // the tasks share the 1024 partial rows of the workspace
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(conv0_wgrad_kernel, dim3(nb, tasks), dim3(256), (size_t)lds, s, x, dy, workspace, B, T, F, sX);
-    hipLaunchKernelGGL(conv0_wgrad_final_kernel, dim3(160, tasks), dim3(256), 0, s, workspace, nb, dw, db, sDw, sDb);
+    if (C == 64)
+        hipLaunchKernelGGL(conv0_wgrad_kernel<64>, dim3(nb, tasks), dim3(256), (size_t)lds, s, x, dy, workspace, B, T, F, sX);
+    else
+        hipLaunchKernelGGL(conv0_wgrad_kernel<32>, dim3(nb, tasks), dim3(256), (size_t)lds, s, x, dy, workspace, B, T, F, sX);
+    hipLaunchKernelGGL(conv0_wgrad_final_kernel, dim3(C * 10 / 4, tasks), dim3(256), 0, s, workspace, nb, dw, db, C * 10, sDw, sDb);
     MTL_CHECK_LAUNCH();
     return MTL_OK;
 }
 
+int mtl_conv0_wgrad_tb(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int tasks,
+                       long sX, long sDw, long sDb) {
+    return conv0_wgrad(as_stream(stream), x, dy, dw, db, workspace, B, T, F, 64, tasks, sX, sDw, sDb);
+}
+
 int mtl_conv0_wgrad(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F) {
-    if (!x || !dy || !dw || !db || !workspace) return MTL_EINVAL;
-    const long lds = std::max<long>((long)C0_NB * (F + 2) * C0_ROW * 4, 16L * 640 * 4);
-    if (B <= 0 || T <= 0 || F <= 0 || lds > 64 * 1024) return MTL_EINVAL;
-    const long tiles = (long)B * ((T + C0_TB - 1) / C0_TB);
-    const int nb = (int)std::min<long>((tiles + C0_NB - 1) / C0_NB, 1024);
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(conv0_wgrad_kernel, dim3(nb), dim3(256), (size_t)lds, s, x, dy, workspace, B, T, F);
-    hipLaunchKernelGGL(conv0_wgrad_final_kernel, dim3(160), dim3(256), 0, s, workspace, nb, dw, db);
-    MTL_CHECK_LAUNCH();
-    return MTL_OK;
+    return conv0_wgrad(as_stream(stream), x, dy, dw, db, workspace, B, T, F, 64, 1, 0, 0, 0);
+}
+
+int mtl_conv0c_wgrad_tb(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int C,
+                        int tasks, long sX, long sDw, long sDb) {
+    return conv0_wgrad(as_stream(stream), x, dy, dw, db, workspace, B, T, F, C, tasks, sX, sDw, sDb);
+}
+
+int mtl_conv0c_wgrad(void* stream, const float* x, const float* dy, float* dw, float* db, float* workspace, int B, int T, int F, int C) {
+    return conv0_wgrad(as_stream(stream), x, dy, dw, db, workspace, B, T, F, C, 1, 0, 0, 0);
 }
 
 int mtl_permute_hc_tb(void* stream, const float* src, float* dst, int rows, int C, int Hh, int inverse_accum, float* amax, int tasks,

@@ -21,6 +21,7 @@
 
 #include "mtl_common.h"
 #include "mtl_h2.h"
+#include "mtl_conv_narrow.h"
 #include "../../include/mtl_hip.h"
 
 namespace {
@@ -1747,8 +1748,15 @@ int launch_conv_x3h(ConvX3P p, int Te, int Fe, hipStream_t s) {
     return MTL_OK;
 }
 
+static_assert(EPI_RELU == NARROW_RELU && EPI_POOL == NARROW_POOL && EPI_DGRAD == NARROW_DGRAD, "one numbering of the epilogues");
+
 template <bool UNPOOL, int EPI, int NP>
 int dispatch_conv_x3(ConvX3P& p, int Te, int Fe, hipStream_t s) {
+    if constexpr (NP == 3) {      // the 32-channel shapes of the large_cnn front-end: mtl_conv_narrow.hip (exact split only)
+        if (narrow_conv_serves(p.g.Cin, p.g.Cout, UNPOOL, EPI))
+            return narrow_conv_launch(s, NarrowConvP{p.x, p.am_in, p.w3, p.bias, p.act, p.y, p.am_out, p.g.B, p.g.T, p.g.F, p.g.Cin, p.g.Cout,
+                                                     p.g.Tp, p.g.Fp, Te, Fe, p.Bt, p.sW, p.sBias, p.widths, p.wshift, 0, 0}, UNPOOL, EPI);
+    }
     if (p.g.Cin % 64 || p.g.Cout % 64) return MTL_EINVAL;     // C_in % 64: even number of K-tiles (producer loop is unrolled by 2)
     // 8 x 16 tiles (G = 1: 79 KiB of LDS at BN = 64, two workgroups per CU) measured faster only on the 64 -> 64 layer
     // (conv2 fwd 0.52 -> 0.50 ms, dgrad 0.61 -> 0.59); every 128-wide shape and conv5-dgrad is faster with 16 x 16 tiles.
@@ -3119,6 +3127,7 @@ long mtl_conv3x3_wgrad_x3_workspace(int B, int T, int F, int Cin, int Cout, int 
     (void)T;
     (void)F;
     (void)pooled;
+    if (narrow_wgrad_serves(Cin, Cout)) return narrow_wgrad_slots() * (9L * Cin * Cout * 4 + Cout * 4);      // (exact split only)
     if (Cin % 64 || Cout % 64) return 0;
     const int npairs = (Cin / 64) * (Cout / 64);
     const long nslots = wgrad_x3_grid(Cin, Cout) / npairs;
@@ -3136,6 +3145,22 @@ template <int NP>
 static int wgrad_pieces(hipStream_t s, const float* x, const float* amax_x, const float* dy, const float* amax_dy,
                         const unsigned char* argmax, float* dw_ref, float* db, float* workspace, long workspace_bytes, int B, int T,
                         int F, int Cin, int Cout, WgradTasks tk = WgradTasks{1, 0, 0, 0, 0}) {
+    if constexpr (NP == 3) {      // the 32-channel shapes of the large_cnn front-end: mtl_conv_narrow.hip, one slab per workgroup
+        if (narrow_wgrad_serves(Cin, Cout)) {
+            const int slots = narrow_wgrad_slots(), pooled = argmax != nullptr;
+            if (!x || !dy || !dw_ref || !workspace || B < 1 || tk.tasks < 1 || tk.tasks > slots) return MTL_EINVAL;
+            if (workspace_bytes < mtl_conv3x3_wgrad_x3_workspace(B, T, F, Cin, Cout, pooled)) return MTL_EINVAL;
+            const int Ty = pooled ? 2 * (T / 2) : T, Fy = pooled ? 2 * (F / 2) : F;
+            if (Ty <= 0 || Fy <= 0) return MTL_OK;               // empty extent: dw / db keep their values, no launch
+            float* bias_part = db ? workspace + (long)slots * 9L * Cin * Cout : nullptr;
+            const int rc = narrow_wgrad_launch(s, NarrowWgradP{x, dy, argmax, workspace, bias_part, B, T, F, Ty, Fy, T / 2, F / 2, Cout, tk.tasks, 0, 0, 0});
+            if (rc) return rc;
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * Cin * Cout + (db ? Cout : 0) + 63) / 64, tk.tasks), dim3(1024), 0, s, workspace, dw_ref,
+                               slots / tk.tasks, Cin, Cout, bias_part, db, tk.sDw, tk.sDb);
+            MTL_CHECK_LAUNCH();
+            return MTL_OK;
+        }
+    }
     if (!x || !dy || !dw_ref || !workspace || Cin % 64 || Cout % 64 || (NP == 2 && (!amax_x || !amax_dy))) return MTL_EINVAL;
     if (tk.tasks < 1 || tk.tasks > wgrad_x3_grid(Cin, Cout) / ((Cin / 64) * (Cout / 64))) return MTL_EINVAL;
     const int pooled = argmax != nullptr;

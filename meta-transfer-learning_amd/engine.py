@@ -444,6 +444,7 @@ class PassEngine:
             raise ValueError('MTL_CONV must be h2, x3 or f32')
         self.conv_x3 = self.conv_mode != 'f32'
         self.conv_h2 = self.conv_mode == 'h2'
+        self.conv_layers = convstack.layers_for(layout)     # vgg_cnn or large_cnn (the latter: always 'x3', convstack.decide)
         self._ln_pending, self._ln_tables = [], {}
         # the encoder's input Linear (5120 -> 512) with its data / weight gradient: 'h2' with the h2 convolutions (two fp16 pieces, the
         # bounds ride along), else the product engines' own routing (x3 / fp32); bench.py's exact-fp32 leg sets 'f32'
@@ -1298,7 +1299,7 @@ frames=frames, widths=widths, seed=seed, B=B, T=T, Td=Td, nt=nt, n_nonpad=n_nonp
         if Bx not in (B, nt * B) or T != meta['T']:
             raise ValueError('input batch does not match the prepared batch')
         sX = B * F * T if Bx == nt * B and nt > 1 else 0          # task stride of the input (0: one batch shared by all tasks)
-        if F // 2 // 2 * 128 != hp.d_in:
+        if F // 2 // 2 * self.conv_layers[-1].cout != hp.d_in:
             raise ValueError('dim_input %d does not match %d frequency bins' % (hp.d_in, F))
         if loss_type not in LOSS_TYPES:
             raise NotImplementedError("loss_type must be 'ce' or 'ctc'")

@@ -166,19 +166,21 @@ class _ModelEncFn(torch.autograd.Function):
 class Transformer(nn.Module):
     def __init__(self, encoder, decoder, vocab, feat_extractor='vgg_cnn', train=True, is_factorized=False, r=100):
         super().__init__()
-        if feat_extractor != 'vgg_cnn':
-            raise NotImplementedError("only feat_extractor='vgg_cnn' is on the accelerated path")
+        if feat_extractor not in ('vgg_cnn', 'large_cnn'):
+            raise NotImplementedError("only feat_extractor='vgg_cnn' and 'large_cnn' are on the accelerated path")
         self.encoder, self.decoder, self.vocab = encoder, decoder, vocab
         self.feat_extractor, self.is_factorized, self.r = feat_extractor, is_factorized, r
         self.copy_grad = None
         if encoder.dropout_rate != decoder.dropout_rate:
             raise ValueError('encoder and decoder are built with one --dropout value in the reference factory')
         print('feat extractor:', feat_extractor)
-        # indices 0,2,5,7 hold the convolutions exactly like the reference nn.Sequential (ReLU/MaxPool are parameter-free)
-        self.conv = nn.Sequential(nn.Conv2d(1, 64, 3, stride=1, padding=1), nn.ReLU(),
-                                  nn.Conv2d(64, 64, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2),
-                                  nn.Conv2d(64, 128, 3, stride=1, padding=1), nn.ReLU(),
-                                  nn.Conv2d(128, 128, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2))
+        # indices 0,2,5,7 hold the convolutions exactly like the reference nn.Sequential (ReLU/MaxPool are parameter-free);
+        # large_cnn (models/asr/transformer.py:60-72): the same stack at half the width
+        c1, c2 = (64, 128) if feat_extractor == 'vgg_cnn' else (32, 64)
+        self.conv = nn.Sequential(nn.Conv2d(1, c1, 3, stride=1, padding=1), nn.ReLU(),
+                                  nn.Conv2d(c1, c1, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2),
+                                  nn.Conv2d(c1, c2, 3, stride=1, padding=1), nn.ReLU(),
+                                  nn.Conv2d(c2, c2, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2))
         for p in self.parameters():
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)

@@ -20,7 +20,7 @@ from collections import deque
 
 import torch
 
-from . import _lib, _trace, dist as mdist, hostenv
+from . import _lib, _trace, convstack, dist as mdist, hostenv
 from .engine import CENSUS_NAMES, CENSUS_SLOTS, PAD_ID, round_width
 from .discriminator import calculate_adversarial, calculate_multi_task, save_discriminator
 from .functions import post_process, save_joint_model, save_meta_model
@@ -897,6 +897,8 @@ class TransientTrainer():
         self._census_on = None
         engs = getattr(model, 'engines', None)
         if not engs or self.h2_check_every <= 0 or not all(e.conv_h2 for e in engs) or any(e.prof is not None for e in engs):
+            return None
+        if any(convstack.decide(e, 1, None)['conv_mode'] != 'h2' for e in engs):      # (a large_cnn model: no h2 operand to count)
             return None
         self._h2_iter += 1
         if (self._h2_iter - 1) % self.h2_check_every:
