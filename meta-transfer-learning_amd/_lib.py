@@ -331,6 +331,57 @@ class Recorder:
         return fn
 
 
+class Replay:
+    """Eager, then recorded, then replayed: the rule the decoders apply to a fixed sequence of library calls.  Under at most `capacity`
+    keys (everything the recorded addresses and arguments depend on; the oldest inserted key is evicted first) any number of units
+    (a whole greedy decode, one position, one block of positions).  `run = replay.begin(eng, key)` once per search, then `run(unit, body)`:
+    body() runs eagerly at the unit's first sighting, at the second with eng.lib replaced by a Recorder, and from the third on the
+    recorded CommandList runs in its place.  Recorded lists hold raw addresses: an entry made at another eng.scratch_epoch starts
+    over, a list is kept only if the epoch did not move while it was recorded, and a search under which the epoch moves finishes
+    eagerly.  While eng.prof is set or eng.lib is a Recorder already, body() runs directly and nothing here changes."""
+
+    def __init__(self, capacity):
+        self.capacity, self._entries = int(capacity), {}
+
+    def keys(self):
+        return list(self._entries)
+
+    def recorded(self, key=None):
+        """the finished CommandLists of `key` (default: of every key)"""
+        ents = self._entries.values() if key is None else [self._entries[key]] if key in self._entries else []
+        return [cl for ent in ents for cl in ent['lists'].values()]
+
+    def begin(self, eng, key):
+        ent = None
+        bypass = lambda: eng.prof is not None or isinstance(eng.lib, Recorder)
+        if not bypass():
+            ent = self._entries.get(key)
+            if ent is None or ent['epoch'] != eng.scratch_epoch:
+                self._entries.pop(key, None)
+                while len(self._entries) >= self.capacity:
+                    self._entries.pop(next(iter(self._entries)))
+                ent = self._entries[key] = dict(epoch=eng.scratch_epoch, seen=set(), lists={})
+
+        def run(unit, body):
+            if ent is None or bypass() or ent['epoch'] != eng.scratch_epoch:
+                body()
+            elif unit in ent['lists']:
+                ent['lists'][unit].run()
+            elif unit in ent['seen']:
+                cl, real = CommandList(), eng.lib
+                eng.lib = Recorder(real, cl)
+                try:
+                    body()
+                finally:
+                    eng.lib = real
+                if ent['epoch'] == eng.scratch_epoch:
+                    ent['lists'][unit] = cl.finish()
+            else:
+                ent['seen'].add(unit)
+                body()
+        return run
+
+
 def check(rc, what):
     if rc != 0:
         raise RuntimeError('%s failed with code %d' % (what, rc))

@@ -11,8 +11,6 @@ What a pass computes follows the reference line by line:
   models/asr/transformer.py:120-149 (forward), modules/encoder.py:53-106, modules/decoder.py:71-115,293-323,
   modules/common_layers.py:110-132,238-331, utils/metrics.py:96-126.
 """
-import math
-
 import os
 
 import numpy as np
@@ -20,11 +18,12 @@ import torch
 
 import re
 
-from . import _lib, _trace, convstack
+from . import _lib, _trace, convstack, decode
 from ._lib import check
+from .batchmeta import PAD_ID, SOS_ID, EOS_ID, batch_meta, decoder_io, ctc_input_lengths      # noqa: F401  (callers import the ids and the two helpers from here)
 from .convstack import CENSUS_NAMES, CENSUS_SLOTS      # noqa: F401  (the bound slots of the h2 operands; the trainer's h2 guard names them)
+from .decode import beam_unpack                         # noqa: F401
 
-PAD_ID, SOS_ID, EOS_ID = 0, 1, 2
 RELU, ACCUM = 1, 2
 
 
@@ -72,284 +71,8 @@ class Hyper:
         self.__dict__.update(kw)
 
 
-def decoder_io(padded_target, pad_id=PAD_ID, sos_id=SOS_ID, eos_id=EOS_ID, width=None):
-    """modules/decoder.py:55-69 on the host: seq_in = [SOS, y..] padded with EOS; seq_out = [y.., EOS] padded with PAD.
-    width: at least this many decoder positions (a slice of a batch keeps the whole batch's width, so that the labels
-    predicted at padded positions -- which the reference's CER strings include -- are the same)."""
-    tgt = padded_target.detach().to('cpu', torch.int64).numpy()
-    B, L = tgt.shape
-    nonpad = tgt != pad_id
-    lens = nonpad.sum(1)
-    width = max(int(lens.max()) + 1, int(width or 0))
-    # every row's non-pad labels moved to the front in their order (the reference drops pads wherever they stand): a stable
-    # argsort of the pad flags; numpy on these few hundred integers costs a tenth of the per-row tensor indexing it replaces
-    comp = np.take_along_axis(tgt, np.argsort(~nonpad, axis=1, kind='stable'), 1)
-    m = min(L, width - 1)
-    own = np.arange(m)[None, :] < lens[:, None]
-    seq_in = np.full((B, width), eos_id, dtype=np.int64)
-    seq_out = np.full((B, width), pad_id, dtype=np.int64)
-    seq_in[:, 0] = sos_id
-    seq_in[:, 1:m + 1] = np.where(own, comp[:, :m], eos_id)
-    seq_out[:, :m] = np.where(own, comp[:, :m], pad_id)
-    seq_out[np.arange(B), lens] = eos_id
-    return torch.from_numpy(seq_in), torch.from_numpy(seq_out)
-
-
-def ctc_input_lengths(percentages, Td):
-    """utils/metrics.py:129 / transient_trainer.py:38: sizes = src_percentages.mul_(Td).int() -- an fp32 product, truncated (numpy in
-    fp32 reproduces it bit for bit; the caller's tensor is not scaled in place here)."""
-    return (np.asarray(percentages, dtype=np.float32) * np.float32(Td)).astype(np.int32)
-
-
 LOSS_TYPES = ('ce', 'ctc')
 _FULL = {'q': 'query', 'k': 'key', 'v': 'value'}
-
-
-class _DecodeSession:
-    """See PassEngine.decode_session."""
-
-    def __init__(self, eng, theta, mem, B, T4, S, shared_memory, groups=1):
-        self.eng, self.B, self.T4, self.S = eng, B, T4, S
-        # groups > 1 (batched beam search): the B rows are `groups` utterances of B / groups hypothesis rows each, every utterance's
-        # rows sharing ITS encoder memory -- mem is (groups, T4, d)
-        self.groups = int(groups) if shared_memory else 1
-        if B % self.groups:
-            raise ValueError('rows do not divide into %d groups' % self.groups)
-        hp = eng.hp
-        d, r, h, dk, dv, V = hp.d, hp.r, hp.h, hp.dk, hp.dv, hp.V
-        hk, hv = h * dk, h * dv
-        if S > eng.pe_dec.shape[0] + 1:
-            raise ValueError('tgt_max_len too small for %d decoding positions' % S)
-        self.P = theta.data_ptr()
-        buf = eng.buf
-        self.x = buf('g.x', (B, d))
-        # fast path (head sizes of the fused attention kernel, h d_k = h d_v): q / k / v of a layer's self-attention live in ONE (3, B, S, h d_k)
-        # block -- row t of [0] is the current query, [1] / [2] are the K / V caches -- so that the three low-rank projections are two
-        # strided-batch launches writing row t, and the attention over the cache is ONE flash-attention launch (keys beyond the current
-        # position masked by a per-step length: row t of `klen_self`) instead of product + softmax + product
-        self.fast = bool(eng.fused_attn and hk == hv and hp.n_dec > 0 and
-                         eng._qkv_groups('decoder.layers.0.self_attn.', 1, 1, 1, 1, hk, hv)[0][0] == 'qkv')
-        if self.fast:
-            self.qkv = [buf('g.qkv%d' % i, (3, B, S, hk)) for i in range(hp.n_dec)]
-            for c in self.qkv:
-                eng.zero_(c)                                        # (masked keys are multiplied by probability 0: they must be finite)
-            self.kc, self.vc = [c[1] for c in self.qkv], [c[2] for c in self.qkv]
-            self.klen_self = buf('g.klen', (S, B), torch.int32)
-            self.klen_self.copy_(torch.arange(1, S + 1, dtype=torch.int32).view(S, 1).expand(S, B))
-            self.klen_cross = buf('g.klenx', (B,), torch.int32)
-            self.klen_cross.fill_(T4)
-            self.lse = buf('g.lse', (B, h, 1))
-            # the weights do not move during a decode: every rank-r pair  y = (x W_a^T) W_b^T  is applied as ONE product with
-            # W_b W_a (h d_k x d: 1 MB instead of 0.4 MB streamed per step, but one dependent launch instead of two -- a step is a
-            # chain of launches, not a bandwidth problem); merged once per session from the current theta (6 small products per layer)
-            self.Wqkv = [buf('g.wqkv%d' % i, (3, hk, d)) for i in range(hp.n_dec)]
-            self.Wso = [buf('g.wso%d' % i, (d, hv)) for i in range(hp.n_dec)]
-            self.Wcq = [buf('g.wcq%d' % i, (hk, d)) for i in range(hp.n_dec)]
-            self.Wco = [buf('g.wco%d' % i, (d, hv)) for i in range(hp.n_dec)]
-            for i in range(hp.n_dec):
-                pre = 'decoder.layers.%d.' % i
-                o = lambda n, pre=pre: self.P + 4 * eng.L.off(pre + n)
-                sA_, sB_ = (eng._pstride(pre + 'self_attn.', 'qkv', sfx) for sfx in ('_linear_a.weight', '_linear_b.weight'))
-                eng.gemm(0, 0, hk, d, r, o('self_attn.query_linear_b.weight'), r, o('self_attn.query_linear_a.weight'), d, self.Wqkv[i].data_ptr(), d,
-                         batch=3, sA=(sB_, 0), sB=(sA_, 0), sC=(hk * d, 0))
-                for att, dst in (('self_attn.', self.Wso[i]), ('encoder_attn.', self.Wco[i])):
-                    eng.gemm(0, 0, d, hv, r, o(att + 'output_linear_b.weight'), r, o(att + 'output_linear_a.weight'), hv, dst.data_ptr(), hv)
-                eng.gemm(0, 0, hk, d, r, o('encoder_attn.query_linear_b.weight'), r, o('encoder_attn.query_linear_a.weight'), d,
-                         self.Wcq[i].data_ptr(), d)
-        else:
-            self.kc = [buf('g.kc%d' % i, (B, S, hk)) for i in range(hp.n_dec)]
-            self.vc = [buf('g.vc%d' % i, (B, S, hv)) for i in range(hp.n_dec)]
-        Bm = self.groups if shared_memory else B
-        self.cross_stride = 0 if shared_memory else T4
-        self.ck = [buf('g.ck%d' % i, (Bm * T4, hk)) for i in range(hp.n_dec)]
-        self.cv = [buf('g.cv%d' % i, (Bm * T4, hv)) for i in range(hp.n_dec)]
-        self.ta, self.tq = buf('g.ta', (max(Bm * T4, B), r)), buf('g.q', (B, hk))
-        self.to, self.tob = buf('g.o', (B, hv)), buf('g.ob', (B, d))
-        self.y1, self.y2, self.y3 = buf('g.y1', (B, d)), buf('g.y2', (B, d)), buf('g.y3', (B, d))
-        self.h1, self.h2 = buf('g.h1', (B, hp.inner)), buf('g.h2', (B, d))
-        self.xhat, self.rstd = buf('g.xhat', (B, d)), buf('g.rstd', (B,))
-        self.ldS = (max(S, T4) + 3) // 4 * 4
-        self.Sc = buf('g.S', (B, h, 1, self.ldS))
-        self.logits = buf('g.logits', (B, V))
-        self.junk = buf('g.junk', (3 * B + 4,))
-        self.zero_gold = buf('g.zero', (B,), torch.int64)
-        self.zero_gold.zero_()
-        self.cur = [buf('g.cur0', (B, d)), buf('g.cur1', (B, d))]
-        self.last = None
-        for i in range(hp.n_dec):                                   # cross-attention keys / values of the encoder output, once
-            pre = 'decoder.layers.%d.encoder_attn.' % i
-            self._lowrank(pre, 'key', mem, Bm * T4, self.ck[i].data_ptr())
-            self._lowrank(pre, 'value', mem, Bm * T4, self.cv[i].data_ptr(), width=hv)
-
-    def _lowrank(self, pre, name, src, rows, dst, ldc=None, width=None):
-        eng, hp = self.eng, self.eng.hp
-        hk, hv = hp.h * hp.dk, hp.h * hp.dv
-        width = hk if width is None else width
-        o = lambda n: self.P + 4 * eng.L.off(pre + n)
-        eng.linear_fwd(src, rows, hp.d if name != 'output' else hv, o(name + '_linear_a.weight'), None, self.ta.data_ptr(), hp.r)
-        eng.gemm(0, 1, rows, width, hp.r, self.ta.data_ptr(), hp.r, o(name + '_linear_b.weight'), hp.r, dst, ldc or width,
-                 bias=o(name + '_linear_b.bias'))
-
-    def _attend(self, q, kbuf, vbuf, kv_rows, k_stride, v_stride, out):
-        # one query row per (b, h): scores over kv_rows keys, softmax, weighted sum of the values; k_stride / v_stride: floats from one
-        # row's keys / values to the next row's (rows of h d_k and of h d_v floats: two numbers unless d_k = d_v), 0 for a shared memory
-        eng, hp, B = self.eng, self.eng.hp, self.B
-        h, dk, dv = hp.h, hp.dk, hp.dv
-        hk, hv, ldS = h * dk, h * dv, self.ldS
-        eng.gemm(0, 1, 1, kv_rows, dk, q, hk, kbuf, hk, self.Sc.data_ptr(), ldS, batch=B * h, H=h, sA=(hk, dk), sB=(k_stride, dk),
-                 sC=(h * ldS, ldS))
-        check(eng.lib.mtl_softmax_mask_fwd(eng.stream, self.Sc.data_ptr(), None, 0, 1.0 / float(hp.temperature), B, h, 1, kv_rows,
-                                           ldS, None, 1.0, None), 'softmax')
-        eng.gemm(0, 0, 1, dv, kv_rows, self.Sc.data_ptr(), ldS, vbuf, hv, out, hv, batch=B * h, H=h, sA=(h * ldS, ldS),
-                 sB=(v_stride, dv), sC=(hv, dv))
-
-    def _attend_groups(self, q, kbuf, vbuf, kv_rows, out):
-        # cross-attention of `groups` utterances with W = B / groups query rows each: the same two strided-batch products and softmax
-        # as _attend, batch = (utterance, head) with M = W rows per item instead of (row, head) with M = 1
-        eng, hp, B, U = self.eng, self.eng.hp, self.B, self.groups
-        h, dk, dv, W = hp.h, hp.dk, hp.dv, self.B // self.groups
-        hk, hv, ldS = h * dk, h * dv, self.ldS
-        eng.gemm(0, 1, W, kv_rows, dk, q, hk, kbuf, hk, self.Sc.data_ptr(), h * ldS, batch=U * h, H=h, sA=(W * hk, dk),
-                 sB=(kv_rows * hk, dk), sC=(W * h * ldS, ldS))
-        check(eng.lib.mtl_softmax_mask_fwd(eng.stream, self.Sc.data_ptr(), None, 0, 1.0 / float(hp.temperature), B, h, 1, kv_rows,
-                                           ldS, None, 1.0, None), 'softmax')
-        eng.gemm(0, 0, W, dv, kv_rows, self.Sc.data_ptr(), h * ldS, vbuf, hv, out, hv, batch=U * h, H=h, sA=(W * h * ldS, ldS),
-                 sB=(kv_rows * hv, dv), sC=(W * hv, dv))
-
-    def step(self, t, tok_ptr):
-        """Feed the B tokens at device address tok_ptr as position t; leaves the logits of that position in self.logits."""
-        eng, hp, B, S, T4 = self.eng, self.eng.hp, self.B, self.S, self.T4
-        d, V = hp.d, hp.V
-        hk, hv = hp.h * hp.dk, hp.h * hp.dv
-        L, lib, P = eng.L, eng.lib, self.P
-        check(lib.mtl_embed_pe_fwd(eng.stream, tok_ptr, P + 4 * L.off('decoder.trg_embedding.weight'),
-                                   eng.pe_dec.data_ptr() + 4 * t * d, self.x.data_ptr(), B, 1, d, None, 1.0), 'embed')
-        cur = self.x
-        for i in range(hp.n_dec):
-            pre = 'decoder.layers.%d.' % i
-            o = lambda n: P + 4 * L.off(pre + n)
-            sa = pre + 'self_attn.'
-            if self.fast:
-                sb_ = eng._pstride(sa, 'qkv', '_linear_b.bias')
-                qkv = self.qkv[i].data_ptr()
-                eng.gemm(0, 1, B, hk, d, cur.data_ptr(), d, self.Wqkv[i].data_ptr(), d, qkv + 4 * t * hk, S * hk,
-                         bias=o('self_attn.query_linear_b.bias'), batch=3, sB=(hk * d, 0), sC=(B * S * hk, 0), sbias=sb_)
-                check(lib.mtl_attn_fwd(eng.stream, qkv + 4 * t * hk, self.kc[i].data_ptr(), self.vc[i].data_ptr(), S * hk, hk, hv,
-                                       self.klen_self.data_ptr() + 4 * t * B, 0, 1.0 / float(hp.temperature), B, hp.h, 1, S, hp.dk, hp.dv, None, 0,
-                                       1.0, self.to.data_ptr(), hv, self.lse.data_ptr()), 'mtl_attn_fwd')
-            else:
-                self._lowrank(sa, 'query', cur.data_ptr(), B, self.tq.data_ptr())
-                self._lowrank(sa, 'key', cur.data_ptr(), B, self.kc[i].data_ptr() + 4 * t * hk, ldc=S * hk)      # row t of the cache
-                self._lowrank(sa, 'value', cur.data_ptr(), B, self.vc[i].data_ptr() + 4 * t * hv, ldc=S * hv, width=hv)
-                self._attend(self.tq.data_ptr(), self.kc[i].data_ptr(), self.vc[i].data_ptr(), t + 1, S * hk, S * hv, self.to.data_ptr())
-            if self.fast:
-                eng.gemm(0, 1, B, d, hv, self.to.data_ptr(), hv, self.Wso[i].data_ptr(), hv, self.tob.data_ptr(), d,
-                         bias=o('self_attn.output_linear_b.bias'))
-            else:
-                self._lowrank(sa, 'output', self.to.data_ptr(), B, self.tob.data_ptr(), width=d)
-            eng.ln_fwd(self.tob.data_ptr(), cur.data_ptr(), o('self_attn.layer_norm.weight'), o('self_attn.layer_norm.bias'), None, None,
-                       self.y1.data_ptr(), self.xhat.data_ptr(), self.rstd.data_ptr(), B, 1)
-            ca = pre + 'encoder_attn.'
-            if self.fast:
-                eng.gemm(0, 1, B, hk, d, self.y1.data_ptr(), d, self.Wcq[i].data_ptr(), d, self.tq.data_ptr(), hk,
-                         bias=o('encoder_attn.query_linear_b.bias'))
-            else:
-                self._lowrank(ca, 'query', self.y1.data_ptr(), B, self.tq.data_ptr())
-            if self.fast and self.cross_stride:      # (every row has its own memory: greedy search; beam search shares one with stride 0)
-                check(lib.mtl_attn_fwd(eng.stream, self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), hk, hk, hv,
-                                       self.klen_cross.data_ptr(), 0, 1.0 / float(hp.temperature), B, hp.h, 1, T4, hp.dk, hp.dv, None, 0, 1.0,
-                                       self.to.data_ptr(), hv, self.lse.data_ptr()), 'mtl_attn_fwd')
-            elif self.groups > 1:
-                self._attend_groups(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.to.data_ptr())
-            else:
-                self._attend(self.tq.data_ptr(), self.ck[i].data_ptr(), self.cv[i].data_ptr(), T4, self.cross_stride * hk,
-                             self.cross_stride * hv, self.to.data_ptr())
-            if self.fast:
-                eng.gemm(0, 1, B, d, hv, self.to.data_ptr(), hv, self.Wco[i].data_ptr(), hv, self.tob.data_ptr(), d,
-                         bias=o('encoder_attn.output_linear_b.bias'))
-            else:
-                self._lowrank(ca, 'output', self.to.data_ptr(), B, self.tob.data_ptr(), width=d)
-            eng.ln_fwd(self.tob.data_ptr(), self.y1.data_ptr(), o('encoder_attn.layer_norm.weight'), o('encoder_attn.layer_norm.bias'), None,
-                       None, self.y2.data_ptr(), self.xhat.data_ptr(), self.rstd.data_ptr(), B, 1)
-            eng.linear_fwd(self.y2.data_ptr(), B, d, o('pos_ffn.linear_1.weight'), o('pos_ffn.linear_1.bias'), self.h1.data_ptr(), hp.inner,
-                           relu=True)
-            eng.linear_fwd(self.h1.data_ptr(), B, hp.inner, o('pos_ffn.linear_2.weight'), o('pos_ffn.linear_2.bias'), self.h2.data_ptr(), d)
-            nxt = self.cur[i & 1]                  # (the layer's output lands where the next layer reads it: no copy)
-            eng.ln_fwd(self.h2.data_ptr(), self.y2.data_ptr(), o('pos_ffn.layer_norm.weight'), o('pos_ffn.layer_norm.bias'), None, None,
-                       nxt.data_ptr(), self.xhat.data_ptr(), self.rstd.data_ptr(), B, 1)
-            cur = nxt
-        eng.gemm(0, 1, B, V, d, cur.data_ptr(), d, P + 4 * L.off('decoder.output_linear.weight'), d, self.logits.data_ptr(), V)
-        return self.logits
-
-    def argmax_into(self, dst_ptr):
-        """arg-max of the current logits (lowest index on ties) written as B int64 at dst_ptr; log-sum-exp lands in junk[0:B]."""
-        eng, B, V = self.eng, self.B, self.eng.hp.V
-        check(eng.lib.mtl_ce_argmax_fwd(eng.stream, self.logits.data_ptr(), self.zero_gold.data_ptr(), B, V, V, PAD_ID, 0.0, 1, None,
-                                        self.junk.data_ptr(), dst_ptr, self.junk.data_ptr() + 4 * B, self.junk.data_ptr() + 8 * B),
-              'argmax')
-
-    def logits_and_lse(self):
-        """(B,V) logits and (B,) log-sum-exp of the current position on the host (one synchronising copy each)."""
-        hyp = self.eng.buf('g.hyp', (self.B,), torch.int64)
-        self.argmax_into(hyp.data_ptr())
-        return self.logits.cpu(), self.junk[:self.B].cpu()
-
-    def reorder(self, rows, t):
-        """caches[r, :t] <- caches[rows[r], :t] for every layer (beam search: row r continues hypothesis rows[r])."""
-        if list(rows) == list(range(self.B)):
-            return
-        idx = torch.tensor(rows, dtype=torch.int64, device=self.logits.device)
-        for c in self.kc + self.vc:
-            c[:, :t] = c.index_select(0, idx)[:, :t]
-
-    def gather_tables(self):
-        """device tables of the K / V cache addresses for mtl_beam_gather: [(table, caches, width)], one entry when h d_k = h d_v"""
-        eng, hp = self.eng, self.eng.hp
-        hk, hv = hp.h * hp.dk, hp.h * hp.dv
-        sets = [(self.kc + self.vc, hk)] if hk == hv else [(self.kc, hk), (self.vc, hv)]
-        out = []
-        for j, (caches, width) in enumerate(sets):
-            tab = eng.buf('g.tab%d' % j, (len(caches),), torch.int64)
-            tab.copy_(torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64))
-            out.append((tab, len(caches), width))
-        self.gtmp = eng.buf('g.gtmp', (max(n for _t, n, _w in out) * self.B * self.S * max(hk, hv),))
-        return out
-
-    def gather(self, tables, parent_ptr, t):
-        """caches[r, :t] <- caches[parent[r], :t] for every layer, parent (B,) int32 in device memory (reorder() without the host)"""
-        eng = self.eng
-        for tab, n, width in tables:
-            check(eng.lib.mtl_beam_gather(eng.stream, tab.data_ptr(), n, parent_ptr, self.gtmp.data_ptr(), self.gtmp.numel(), self.B, t, width,
-                                          self.S * width), 'mtl_beam_gather')
-
-
-def beam_unpack(state, U, W, S, start_token, eos_id):
-    """host side of mtl_beam_rank's state (include/mtl_hip.h): per utterance the ended hypotheses in the order they ended, as dicts
-    with 'score' (numpy fp32) and 'yseq' (start token ... EOS), rebuilt from the back-pointer and token tables"""
-    import numpy as np
-    state = np.ascontiguousarray(state, dtype=np.int32)
-    o_bp = 4 * U + U * W
-    o_tk = o_bp + U * S * W
-    o_en = o_tk + U * S * W
-    bp = state[o_bp:o_tk].reshape(U, S, W)
-    tk = state[o_tk:o_en].reshape(U, S, W)
-    en = state[o_en:o_en + 5 * U * S * W].reshape(U, S * W, 5)
-    out = []
-    for u in range(U):
-        def seq(i, r):
-            rev = []
-            while i > 0:
-                rev.append(int(tk[u, i - 1, r]))
-                r = int(bp[u, i - 1, r])
-                i -= 1
-            return [int(start_token)] + rev[::-1]
-        ended = []
-        for e in en[u, :int(state[4 * u + 2])]:
-            yseq = seq(int(e[0]), int(e[2])) + [int(e[3])] + ([int(eos_id)] if e[4] else [])
-            ended.append(dict(score=e[1:2].view(np.float32)[0], yseq=yseq))
-        out.append(ended)
-    return out
-
 
 STAGE_RING = 6      # pinned staging buffers per slot (prepare_tasks): > pipeline depth (default 2) + 2
 
@@ -457,6 +180,10 @@ class PassEngine:
         # gradients at grad + t * sG (see forward_device / backward)
         self.nt, self.sP, self.sG = 1, 0, 0
         self.prof = None    # set (to anything) while a profiling proxy stands in for self.lib: replay / graphs / lane tricks are bypassed
+        # recorded call sequences of the searches (decode.py): greedy (one unit per decode), host-ranked beam (one per position),
+        # device-ranked beam (one per block of BEAM_POLL positions); beam_pin: pinned read-back of the latter's done flags
+        self.replay_greedy, self.replay_beam, self.replay_beam_batch = (_lib.Replay(n) for n in (4, 2, 4))
+        self.beam_pin = None
         if device.type != 'cuda':
             raise RuntimeError('PassEngine needs an MI355X device (got %s); there is no CPU product path' % device)
 
@@ -1123,82 +850,11 @@ class PassEngine:
         percentages = lengths / max(lengths) as data.py forms them, target_sizes = the count of non-PAD targets.  The two int32
         arrays (nt * B each) stand at the END of the meta block."""
         hp = self.hp
-        nt = len(batches)
-        T4 = (T // 2) // 2
-        if frames is not None:
-            frames = [int(f) for f in frames]
-            if len(frames) != nt or max(frames) > T or min(frames) < 4:
-                raise ValueError('frames: one count per task, none above the padded width')
-            if all(f == T for f in frames):
-                frames = None
-        ios = [decoder_io(target, width=width) for _lengths, target in batches]
-        Td = max(io[0].shape[1] for io in ios)
-        if nt > 1 and any(io[0].shape[1] != Td for io in ios):
-            ios = [decoder_io(target, width=Td) for _lengths, target in batches]
-        if T4 > hp.src_max_len or Td > hp.tgt_max_len:
-            raise ValueError('sequence longer than the positional tables')
-        pos = np.arange(T4)[None, :]
-        dpos = np.arange(Td)[None, :]
-        inv, klen_e, klen_d, keep_e, keep_d, firsts, nexts, n_nonpads = [], [], [], [], [], [], [], []
-        ctc_in, ctc_tg = [], []
-        for given in (percentages, target_sizes):
-            if given is not None and len(given) != nt:
-                raise ValueError('percentages / target_sizes: one entry per task')
-        host = lambda v: v.detach().to('cpu').numpy() if torch.is_tensor(v) else np.asarray(v)
-        for ti, ((lengths, _target), (seq_in_t, seq_out_t)) in enumerate(zip(batches, ios)):
-            seq_in, seq_out = seq_in_t.numpy(), seq_out_t.numpy()
-            if seq_in.shape[0] != B:
-                raise ValueError('every task of a batched pass must bring %d samples' % B)
-            lens = lengths.detach().to('cpu', torch.int64).numpy()
-            n_lab = (seq_out != PAD_ID).sum(1) - 1                  # labels per utterance (seq_out = labels, EOS, PAD...)
-            pct = host(percentages[ti]) if percentages is not None and percentages[ti] is not None else \
-                (lens / float(max(int(lens.max()), 1))).astype(np.float32)
-            sizes = host(target_sizes[ti]) if target_sizes is not None and target_sizes[ti] is not None else n_lab
-            if pct.shape != (B,) or sizes.shape != (B,):
-                raise ValueError('percentages / target_sizes: one value per sample')
-            ctc_in.append(ctc_input_lengths(pct, int(n_lab.max()) + 1))
-            ctc_tg.append(sizes.astype(np.int32))
-            if frames is not None:
-                lens = np.minimum(lens, (frames[ti] // 2) // 2)     # a position the task's own pass does not have is padding
-            is_pad = seq_in == EOS_ID
-            dec_len = (~is_pad).sum(1)
-            if not bool((is_pad == (dpos >= dec_len[:, None])).all()):
-                raise ValueError('EOS inside a target sequence is not supported')
-            # occurrence chains of the decoder input ids (deterministic embedding scatter-add, mtl_embed_bwd); row numbers are
-            # those of the whole pass, chains stay inside their task
-            flat_in = seq_in.reshape(-1)
-            order = np.argsort(flat_in, kind='stable')
-            srt = flat_in[order]
-            same_as_prev = np.zeros(srt.shape, dtype=bool)
-            same_as_prev[1:] = srt[1:] == srt[:-1]
-            first = np.empty(flat_in.shape, dtype=np.int32)
-            first[order] = ~same_as_prev
-            nxt = np.full(flat_in.shape, -1, dtype=np.int32)
-            base = ti * B * Td
-            nxt[order[:-1]] = np.where(same_as_prev[1:], order[1:] + base, -1)
-            n_nonpad = int((seq_out != PAD_ID).sum())
-            if norm_count is not None:        # this is a slice of a larger batch: normalise the loss by the WHOLE batch's token count
-                n_nonpad = int(norm_count)
-            n_nonpads.append(n_nonpad)
-            inv.append(1.0 / n_nonpad)
-            klen_e.append(np.minimum(lens, T4).astype(np.int32))               # klen_enc (B)      (SURVEY Q2: raw lengths)
-            klen_d.append(dec_len.astype(np.int32))                            # klen_dec (B)
-            keep_e.append((pos < lens[:, None]).astype(np.int32).reshape(-1))  # keep_enc (B*T4)
-            keep_d.append((~is_pad).astype(np.int32).reshape(-1))              # keep_dec (B*Td)
-            firsts.append(first)
-            nexts.append(nxt)
-        head = 2 + nt + (nt & 1)              # seed (8 bytes) | 1 / n_nonpad per task | padding to an even count
-        # (numpy from here to the upload: a torch CPU kernel on > 32768 elements -- the staging copy was one -- starts an OpenMP
-        # region on torch's whole intra-op pool; in a CPU-quota'd container that stalls the enqueueing thread, hostenv.py)
-        meta_np = np.concatenate([
-            torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).numpy().view(np.int32),   # dropout seed of this pass (torch CPU RNG), 8-byte aligned
-            np.asarray(inv, dtype=np.float32).view(np.int32),                            # 1/n_nonpad (fp32 bits), per task
-            np.zeros(head - 2 - nt, dtype=np.int32)] + klen_e + klen_d + keep_e + keep_d + firsts + nexts
-            + ([np.asarray(frames, dtype=np.int32)] if frames is not None else []) + ctc_in + ctc_tg)
-        n_meta = int(meta_np.shape[0])
-        seq_in = torch.cat([io[0] for io in ios]) if nt > 1 else ios[0][0]
-        seq_out = torch.cat([io[1] for io in ios]) if nt > 1 else ios[0][1]
-        Bt = nt * B
+        bm = batch_meta(batches, B, T, hp.src_max_len, hp.tgt_max_len, norm_count, width, frames, percentages, target_sizes)
+        meta_np, off, Td, nt = bm['meta'], bm['off'], bm['Td'], len(batches)
+        # dropout seed of this pass (torch CPU RNG): drawn once the batch has been accepted
+        meta_np[off['seed']:off['seed'] + 2] = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).numpy().view(np.int32)
+        n_meta, Bt = int(meta_np.shape[0]), nt * B
         # page-locked staging (a ring of STAGE_RING buffers per slot, each guarded by an event): the uploads are truly asynchronous
         # and the host never rewrites a staging buffer whose copy has not been consumed yet.  The ring is deeper than the host may
         # run ahead (pipeline depth + the iteration being resolved + 1), so the event wait never waits in the steady state.
@@ -1228,26 +884,17 @@ class PassEngine:
         i32_np, ids_np = st_i32.numpy(), st_ids.numpy()          # views of the pinned memory
         _trace.mark('stage_wait')
         np.copyto(i32_np, meta_np)
-        np.copyto(ids_np[0], seq_in.numpy())
-        np.copyto(ids_np[1], seq_out.numpy())
+        np.copyto(ids_np[0], bm['seq_in'])
+        np.copyto(ids_np[1], bm['seq_out'])
         dev_i32.copy_(st_i32, non_blocking=True)
         ids.copy_(st_ids, non_blocking=True)
         st['ev'].record(torch.cuda.current_stream(self.device))
         _trace.mark('stage_upload')
-        seed = dev_i32.data_ptr()
-        inv_count = seed + 8
-        klen_enc = seed + 4 * head
-        klen_dec = klen_enc + 4 * Bt
-        keep_enc = klen_dec + 4 * Bt
-        keep_dec = keep_enc + 4 * Bt * T4
-        embed_first = keep_dec + 4 * Bt * Td
-        embed_next = embed_first + 4 * Bt * Td
-        widths = embed_next + 4 * Bt * Td if frames is not None else None
-        ctc_in_len = seed + 4 * (n_meta - 2 * Bt)
-        return dict(ctc_in_len=ctc_in_len, ctc_tgt_len=ctc_in_len + 4 * Bt, ctc_in_len_host=ctc_in, ctc_tgt_len_host=ctc_tg,
-frames=frames, widths=widths, seed=seed, B=B, T=T, Td=Td, nt=nt, n_nonpad=n_nonpads[0], n_nonpads=n_nonpads, gold_host=seq_out,
-                    gold_hosts=[io[1] for io in ios], ids=ids, klen_enc=klen_enc, klen_dec=klen_dec,
-                    keep_enc=keep_enc, keep_dec=keep_dec, embed_first=embed_first, embed_next=embed_next, inv_count=inv_count)
+        base = dev_i32.data_ptr()
+        addr = {name: None if o is None else base + 4 * o for name, o in off.items()}     # device address of every field of the block
+        return dict(addr, frames=bm['frames'], B=B, T=T, Td=Td, nt=nt, n_nonpad=bm['n_nonpads'][0], n_nonpads=bm['n_nonpads'],
+                    gold_host=torch.from_numpy(bm['seq_out']), gold_hosts=bm['gold_hosts'], ids=ids,
+                    ctc_in_len_host=bm['ctc_in_len_host'], ctc_tgt_len_host=bm['ctc_tgt_len_host'])
 
     def forward(self, theta, x, lengths, target, smoothing=0.0, slot=0, loss_type='ce', percentages=None, target_sizes=None):
         """x (B,1,F,T) fp32 on device; lengths (B) int; target (B,L) int64 PAD-padded.  Returns a dict with device
@@ -1413,248 +1060,13 @@ frames=frames, widths=widths, seed=seed, B=B, T=T, Td=Td, nt=nt, n_nonpad=n_nonp
         return dict(pred=pred, gold=ids[1], hyp=hyp, loss=loss, gold_host=meta['gold_host'], n_nonpad=n_nonpad, T4=T4,
                     frames=meta.get('frames'))
 
-    # ---------------------------------------------------------------- greedy decoding
-    def decode_session(self, theta, mem, B, T4, S, shared_memory=False, groups=1):
-        """K/V-cached incremental decoder over `B` hypothesis rows and up to `S` positions (greedy and beam search share it).
-        mem: device pointer of the encoder output, (B, T4, d) -- or (1, T4, d) with shared_memory=True, when all rows are
-        hypotheses of ONE utterance (beam search) and address the same cross-attention keys / values with batch stride 0."""
-        return _DecodeSession(self, theta, mem, B, T4, S, shared_memory, groups)
-
-    def greedy_decode(self, theta, mem, B, T4, start_token, max_steps=300):
-        """Decoder.greedy_search (modules/decoder.py:131-185) on the device: max_steps arg-max steps from `start_token`,
-        no padding masks (the reference passes dec_enc_attn_mask=None and an all-ones non_pad_mask), only causality.
-        The reference re-runs the whole decoder on the growing prefix at every step; here each layer keeps a K/V cache
-        and only the new position is computed (same per-row arithmetic), and the chosen token is fed back through device
-        memory, so the 300 steps run without a single host synchronisation.  Returns the (max_steps, B) int64 token ids."""
-        if max_steps + 1 > self.hp.tgt_max_len:
-            raise ValueError('tgt_max_len too small for %d decoding steps' % max_steps)
-        ses = self.decode_session(theta, mem, B, T4, max_steps + 1)          # (eager: cache zeroing, cross-attention keys / values)
-        ys = self.buf('g.ys', (max_steps + 1, B), torch.int64)
-        ys[0].fill_(int(start_token))
-
-        def steps():
-            for t in range(max_steps):
-                ses.step(t, ys.data_ptr() + 8 * t * B)
-                ses.argmax_into(ys.data_ptr() + 8 * (t + 1) * B)
-        # The ~64 launches of a step cost the host more (8 us each through ctypes) than the device (a decode was host-bound at 0.53 ms
-        # per step): the calls of all steps are recorded once per (parameters, shapes, buffers) into ONE command list -- every address is
-        # fixed: the session's buffers come from the pool by name and shape -- and replayed from C (first sighting: plain eager run,
-        # second: recorded, like TransientTrainer._run_recorded).
-        key = (theta.data_ptr(), int(mem), B, T4, max_steps, ys.data_ptr(), self.stream, self.scratch_epoch, ses.fast)
-        lists = self.__dict__.setdefault('_decode_lists', {})
-        ent = lists.get(key)
-        if self.prof is not None or isinstance(self.lib, _lib.Recorder):
-            steps()
-        elif ent is None:
-            while len(lists) >= 4:
-                lists.pop(next(iter(lists)))
-            lists[key] = 'warm'
-            steps()
-        elif ent == 'warm':
-            cl, real = _lib.CommandList(), self.lib
-            self.lib = _lib.Recorder(real, cl)
-            try:
-                steps()
-            finally:
-                self.lib = real
-            if key[7] == self.scratch_epoch:
-                lists[key] = cl.finish()
-        else:
-            ent.run()
-        return ys[1:]
-
-    def beam_decode(self, theta, mem_row, T4, start_token, beam_width, nbest, tgt_max_len, num_words, eos_id=EOS_ID, c_weight=1.0,
-                    ended_out=None):
-        """Decoder.beam_search (modules/decoder.py:187-291, no LM rescoring) for ONE utterance: the host keeps the reference's
-        hypothesis bookkeeping verbatim in behaviour (expansion order, stable sorts, cumulative truncation to the beam, EOS
-        forced at step T' - 1, final_score = score + sqrt(num_words) * c_weight, fp32 score arithmetic); the device runs one
-        K/V-cached decoder step for all live hypotheses per iteration (caches re-ordered by parent) and returns the last
-        position's logits and log-sum-exp.  num_words(yseq) -> int is the caller's word counter (it needs the vocabulary).
-        -> list of (yseq incl. start token and EOS, final_score) sorted best first, at most nbest.
-        ended_out: a list that receives EVERY ended hypothesis in the order it ended, as dicts with 'score' (fp32, the decoder's
-        log-probability) and 'yseq' (the caller's LM rescoring re-ranks them, modules/decoder.py:248-256)."""
-        import numpy as np
-        W = int(beam_width)
-        steps = int(tgt_max_len)
-        if steps > self.pe_dec.shape[0] or W < 1:
-            raise ValueError('bad beam search arguments')
-        ses = self.decode_session(theta, mem_row, W, T4, steps, shared_memory=True)
-        toks = self.buf('b.tok', (W,), torch.int64)
-        hyp_buf = self.buf('g.hyp', (W,), torch.int64)
-        # the device side of position i (one decoder step for the W rows + log-sum-exp) is the same call sequence for every utterance:
-        # eager at its first sighting, recorded into a command list at the second, replayed from C afterwards (as greedy_decode does for
-        # all its steps at once; here the host ranks the hypotheses between two positions, so there is one list per position)
-        key = ('beam', theta.data_ptr(), W, T4, steps, toks.data_ptr(), self.stream, ses.fast)
-        store = self.__dict__.setdefault('_beam_lists', {})
-        ent = store.get(key)
-        if ent is None or ent['epoch'] != self.scratch_epoch:
-            while len(store) >= 2:
-                store.pop(next(iter(store)))
-            ent = store[key] = dict(epoch=self.scratch_epoch, seen=set(), lists={})
-
-        def body(i):
-            ses.step(i, toks.data_ptr())
-            ses.argmax_into(hyp_buf.data_ptr())                   # (leaves the log-sum-exp of the W rows in ses.junk[:W])
-
-        def device_step(i):
-            cl = ent['lists'].get(i)
-            if self.prof is not None or isinstance(self.lib, _lib.Recorder) or ent['epoch'] != self.scratch_epoch:
-                body(i)
-            elif cl is not None:
-                cl.run()
-            elif i in ent['seen']:
-                cl, real = _lib.CommandList(), self.lib
-                self.lib = _lib.Recorder(real, cl)
-                try:
-                    body(i)
-                finally:
-                    self.lib = real
-                if ent['epoch'] == self.scratch_epoch:
-                    ent['lists'][i] = cl.finish()
-            else:
-                ent['seen'].add(i)
-                body(i)
-        hyps = [dict(score=np.float32(0.0), yseq=[int(start_token)], row=0)]
-        ended = []
-        for i in range(steps):
-            n = len(hyps)
-            rows = [h['row'] for h in hyps] + [0] * (W - n)
-            if i > 0:
-                ses.reorder(rows, i)                              # row r of the caches <- its parent's rows 0..i-1
-            toks.copy_(torch.tensor([h['yseq'][-1] for h in hyps] + [int(eos_id)] * (W - n), dtype=torch.int64))
-            device_step(i)
-            logits, lse = ses.logits.cpu(), ses.junk[:W].cpu()
-            local = (logits[:n] - lse[:n].unsqueeze(1))           # F.log_softmax of the last position, fp32
-            kept = []
-            for r, h in enumerate(hyps):
-                best, ids = torch.topk(local[r], W)
-                for j in range(W):
-                    kept.append(dict(score=np.float32(h['score'] + np.float32(best[j].item())), yseq=h['yseq'] + [int(ids[j])], row=r))
-                kept = sorted(kept, key=lambda x: x['score'], reverse=True)[:W]
-            hyps = kept
-            if i == T4 - 1:
-                for h in hyps:
-                    h['yseq'] = h['yseq'] + [int(eos_id)]
-            live = []
-            for h in hyps:
-                if h['yseq'][-1] == eos_id:
-                    h['final_score'] = np.float32(h['score'] + np.float32(math.sqrt(num_words(h['yseq'])) * c_weight))
-                    ended.append(h)
-                else:
-                    live.append(h)
-            hyps = live
-            if not hyps:
-                break
-        if ended_out is not None:
-            ended_out.extend(dict(score=h['score'], yseq=list(h['yseq'])) for h in ended)
-        out = sorted(ended, key=lambda x: x['final_score'], reverse=True)[:min(len(ended), int(nbest))]
-        return [(h['yseq'], float(h['final_score'])) for h in out]
-
-    BEAM_ROWS = 16      # rows of a batched beam-search session: U = BEAM_ROWS // W utterances per chunk (DESIGN.md "Test-set evaluation")
-    BEAM_POLL = 4       # positions between two reads of the done flags
-
-    def beam_chunk(self, beam_width):
-        """utterances per chunk of beam_decode_batch: U W <= BEAM_ROWS keeps every product of a step on the engine (and within the one
-        row tile) that the W-row session of beam_decode uses"""
-        return max(1, self.BEAM_ROWS // int(beam_width))
-
-    def beam_decode_batch(self, theta, mem_ptr, U, T4, start_token, beam_width, nbest, tgt_max_len, num_words, eos_id=EOS_ID, c_weight=1.0,
-                          ended_out=None, chunk=None):
-        """Decoder.beam_search for U utterances with the hypothesis bookkeeping on the device: per position one K/V-cached decoder step
-        for the rows of a whole chunk of utterances, the log-sum-exp, mtl_beam_rank (candidates, stable global top-W, forced EOS, split
-        into ended / live, back-pointers) and mtl_beam_gather (caches re-ordered by the parents the ranking left in device memory).
-        The host reads no logits: every BEAM_POLL positions it reads the chunk's done flags (one stream synchronisation on a pinned
-        copy), and after the search the ended lists and back-pointer tables in one copy, from which it rebuilds every yseq.
-        mem_ptr: device address of the (U, T4, d) encoder output.  -> per utterance the list beam_decode returns ((yseq, final_score),
-        best first, at most nbest); final_score = fp32(score + fp32(sqrt(num_words(yseq)) c_weight)) and the n-best sort stay on the
-        host (num_words needs the vocabulary's strings).  ended_out: a list of U lists; list u receives every ended hypothesis of
-        utterance u in the order it ended, as dicts with 'score' (fp32) and 'yseq'.  If tgt_max_len < T4 the loop ends without the
-        forced EOS and unended hypotheses are dropped, as in the reference.  chunk: utterances per session (default beam_chunk(W))."""
-        import numpy as np
-        W, steps, U = int(beam_width), int(tgt_max_len), int(U)
-        if steps > self.pe_dec.shape[0] or W < 1 or steps < 1 or U < 1 or (ended_out is not None and len(ended_out) != U):
-            raise ValueError('bad beam search arguments')
-        Uc_max = self.beam_chunk(W) if chunk is None else max(1, int(chunk))
-        results = []
-        for u0 in range(0, U, Uc_max):
-            Uc = min(Uc_max, U - u0)
-            got = self._beam_chunk_search(theta, int(mem_ptr) + 4 * u0 * T4 * self.hp.d, Uc, T4, int(start_token), W, steps, int(eos_id))
-            for u, ended in enumerate(got):
-                for h in ended:
-                    h['final_score'] = np.float32(h['score'] + np.float32(math.sqrt(num_words(h['yseq'])) * c_weight))
-                if ended_out is not None:
-                    ended_out[u0 + u].extend(dict(score=h['score'], yseq=list(h['yseq'])) for h in ended)
-                out = sorted(ended, key=lambda x: x['final_score'], reverse=True)[:min(len(ended), int(nbest))]
-                results.append([(h['yseq'], float(h['final_score'])) for h in out])
-        return results
-
-    def _beam_chunk_search(self, theta, mem, Uc, T4, start_token, W, steps, eos_id):
-        """one chunk of beam_decode_batch -> per utterance the ended hypotheses (dicts: score fp32, yseq) in the order they ended"""
-        import numpy as np
-        lib_, V, B = self.lib, self.hp.V, Uc * W
-        npos = min(steps, T4)                                     # (EOS is forced at position T4 - 1: no position beyond it)
-        words = lib_.mtl_beam_state_words(Uc, W, npos)            # the tables cover the positions that can run, not tgt_max_len
-        if words < 0:
-            raise ValueError('beam search beyond the limits of mtl_beam_rank (include/mtl_hip.h)')
-        ses = self.decode_session(theta, mem, B, T4, steps, shared_memory=True, groups=Uc)
-        tables = ses.gather_tables()
-        state = self.buf('bb.state', (words,), torch.int32)
-        toks = self.buf('bb.tok', (B,), torch.int64)
-        parent = self.buf('bb.par', (B,), torch.int32)
-        hyp_buf = self.buf('g.hyp', (B,), torch.int64)
-        head = 4 * Uc + Uc * W                                    # hdr + score: all a search needs initialised
-        init = np.zeros(head, dtype=np.int32)
-        init[0:4 * Uc:4] = 1                                      # one live row (the start token) with score 0
-        state[:head].copy_(torch.from_numpy(init))
-        t0 = np.full((Uc, W), eos_id, dtype=np.int64)
-        t0[:, 0] = start_token
-        toks.copy_(torch.from_numpy(t0.reshape(-1)))
-        K = self.BEAM_POLL
-
-        def body(i0):
-            for i in range(i0, min(i0 + K, npos)):
-                ses.step(i, toks.data_ptr())
-                ses.argmax_into(hyp_buf.data_ptr())               # (leaves the log-sum-exp of the rows in ses.junk[:B])
-                check(self.lib.mtl_beam_rank(self.stream, ses.logits.data_ptr(), ses.junk.data_ptr(), state.data_ptr(), toks.data_ptr(),
-                                             parent.data_ptr(), i, T4, Uc, W, V, npos, eos_id), 'mtl_beam_rank')
-                if i + 1 < npos:
-                    ses.gather(tables, parent.data_ptr(), i + 1)
-        # every address of a block of K positions is fixed: eager at its first sighting, recorded at the second, replayed afterwards
-        key = ('beamb', theta.data_ptr(), Uc, W, T4, steps, start_token, eos_id, toks.data_ptr(), state.data_ptr(), self.stream, ses.fast)
-        store = self.__dict__.setdefault('_beamb_lists', {})
-        ent = store.get(key)
-        if ent is None or ent['epoch'] != self.scratch_epoch:
-            while len(store) >= 4:
-                store.pop(next(iter(store)))
-            ent = store[key] = dict(epoch=self.scratch_epoch, seen=set(), lists={})
-        pin = self.__dict__.get('_beamb_pin')
-        if pin is None or pin.numel() < 4 * Uc:
-            pin = self._beamb_pin = torch.empty(4 * max(Uc, 16), dtype=torch.int32).pin_memory()
-        for i0 in range(0, npos, K):
-            cl = ent['lists'].get(i0)
-            if self.prof is not None or isinstance(self.lib, _lib.Recorder) or ent['epoch'] != self.scratch_epoch:
-                body(i0)
-            elif cl is not None:
-                cl.run()
-            elif i0 in ent['seen']:
-                cl, real = _lib.CommandList(), self.lib
-                self.lib = _lib.Recorder(real, cl)
-                try:
-                    body(i0)
-                finally:
-                    self.lib = real
-                if ent['epoch'] == self.scratch_epoch:
-                    ent['lists'][i0] = cl.finish()
-            else:
-                ent['seen'].add(i0)
-                body(i0)
-            if i0 + K < npos:
-                pin[:4 * Uc].copy_(state[:4 * Uc], non_blocking=True)
-                torch.cuda.current_stream(self.device).synchronize()
-                if bool((pin[:4 * Uc].view(Uc, 4)[:, 1] != 0).all()):
-                    break
-        host = state.cpu().numpy()                                # (synchronises: the one read-back of the chunk)
-        return beam_unpack(host, Uc, W, npos, start_token, eos_id)
+    # ---------------------------------------------------------------- test-time decoding: decode.py, bound as methods
+    BEAM_ROWS, BEAM_POLL = decode.BEAM_ROWS, decode.BEAM_POLL
+    decode_session = decode.decode_session
+    greedy_decode = decode.greedy_decode
+    beam_decode = decode.beam_decode
+    beam_decode_batch = decode.beam_decode_batch
+    beam_chunk = decode.beam_chunk
 
     def encoder_output(self):
         """(B, T', d) view of the LAST forward's encoder memory (what the decoder attends to; `backward` calls it mem_ptr).  T' is the

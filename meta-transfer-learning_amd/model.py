@@ -4,7 +4,8 @@ compute runs in libmtl_hip.so.
 The nn.Module tree below is a PARAMETER CONTAINER: same attribute names, registration order, constructors and
 initialisers as the reference (so `state_dict()` keys, `parameters()` order and the RNG draw order of the
 initialisation are identical -- SURVEY.md Q4), but no module has a torch forward.  All parameters are views into
-one flat fp32 buffer; `Transformer.forward` hands that buffer to `engine.PassEngine`.
+one flat fp32 buffer; `Transformer.forward` hands that buffer to `engine.PassEngine`, and `Transformer.evaluate` decodes from it
+through the engine's `greedy_decode` / `beam_decode` / `beam_decode_batch` (the searches of `decode.py`).
 
 Reference symbols mirrored: Transformer (models/asr/transformer.py:14-240), Encoder/EncoderLayer
 (modules/encoder.py:15-106), Decoder/DecoderLayer (modules/decoder.py:14-115,293-323),

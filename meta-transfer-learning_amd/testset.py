@@ -1,4 +1,5 @@
-"""Test-set evaluation: the reference's test.py:112-171 `evaluate` loop (CER, WER and the per-language CER over a test loader)."""
+"""Test-set evaluation: the reference's test.py:112-171 `evaluate` loop (CER, WER and the per-language CER over a test loader); the
+hypotheses come from Transformer.evaluate, i.e. the searches of decode.py."""
 import time
 
 import torch

@@ -160,7 +160,7 @@ def test_device_ranked_search_equals_the_host_ranked_search(seed, k, T, L, W, nb
             assert [np.float32(h['score']).tobytes() for h in a] == [np.float32(h['score']).tobytes() for h in b_], rnd
         if tgt >= T4:
             assert all(len(r) >= 1 for r in host)
-    assert any(ent['lists'] for ent in eng._beamb_lists.values())            # the blocks of positions were recorded and replayed
+    assert eng.replay_beam_batch.recorded()                                  # the blocks of positions were recorded and replayed
 
 
 @contextlib.contextmanager

@@ -746,7 +746,7 @@ def test_greedy_decoding_matches_oracle():
         if rep == 1:
             model.evaluate(x.cuda(), lens, y, args, start_token=vocab.SOS_ID, max_steps=steps - 5)
             assert torch.equal(model.last_greedy_ids.t().contiguous(), ref[:, :steps - 5])
-    recorded = [v for v in model.engine._decode_lists.values() if not isinstance(v, str)]
+    recorded = model.engine.replay_greedy.recorded()
     assert len(recorded) == 1 and recorded[0].n >= 12 * steps
     for b in range(3):
         exp = ''
@@ -758,6 +758,45 @@ def test_greedy_decoding_matches_oracle():
     _, gold_ref, _ = oracle(x, lens, y)
     assert golds == [''.join(vocab.id2label[int(t)] for t in row) for row in gold_ref]
     assert model.training                                                   # evaluate() restores the mode
+
+
+def test_searches_record_again_after_the_scratch_buffer_moved():
+    """eager, recorded, replayed; then eng.scratch() is asked for more than it holds (a new buffer and a new scratch_epoch: the recorded
+    lists hold the old address) and the searches go eager, recorded, replayed again -- the same ids six times, and one list per unit
+    under the key afterwards.  Greedy search (3 utterances, 8 steps) and the device-ranked beam search (2 utterances in one chunk, W = 3)."""
+    from oracle import refimpl as R
+    z, cfg, spec = gu.load('F0')
+    mtl_amd, args, vocab, model = make(cfg, spec)
+    model = model.cuda()
+    model.eval()
+    eng, theta = model.engine, model.flat_parameters
+    x, lens, y = R.synth_batch(5, 3, 72, 6, cfg['vocab_size'], True)
+    eng.widen = '0'
+    model.pass_forward(x.cuda(), lens, y)
+    mem, T4 = eng.encoder_output().clone(), (72 // 2) // 2
+    steps, W = 8, 3
+
+    def grow_scratch():
+        held, epoch = eng.arena.get('_scratch'), eng.scratch_epoch
+        eng.scratch((held.numel() * 4 if held is not None else 0) + 4096)
+        assert eng.scratch_epoch == epoch + 1
+
+    def six_times(search, replay):
+        outs, lists = [], []
+        for rnd in range(6):
+            if rnd == 3:
+                grow_scratch()
+            outs.append(search())
+            lists.append(len(replay.recorded(replay.keys()[-1])))
+        assert len(replay.keys()) == 1 and lists[0] == lists[3] == 0 and lists[1] == lists[2] == lists[4] == lists[5] >= 1, lists
+        return outs, lists[5]
+    ids, n = six_times(lambda: eng.greedy_decode(theta, mem.data_ptr(), 3, T4, vocab.SOS_ID, steps).clone(), eng.replay_greedy)
+    assert ids[0].shape == (steps, 3) and all(torch.equal(ids[0], other) for other in ids[1:])
+    assert n == 1 and eng.replay_greedy.recorded()[0].n >= 12 * steps
+    nbest, n = six_times(lambda: eng.beam_decode_batch(theta, mem.data_ptr(), 2, T4, vocab.SOS_ID, W, 2, cfg['tgt_max_len'], model._num_words,
+                                                       vocab.EOS_ID, 1.0, chunk=2), eng.replay_beam_batch)
+    assert len(nbest[0]) == 2 and all(nbest[0] == other for other in nbest[1:])
+    assert n <= -(-T4 // eng.BEAM_POLL)                      # one list per block of positions that ran
 
 
 def test_beam_search_matches_reference_golden_and_oracle():

@@ -286,7 +286,7 @@ GREEDY_STEPS = 40
 
 @pytest.mark.parametrize('name,seed,margin', GREEDY_CASES)
 def test_greedy_search_matches_the_cpu_oracle(name, seed, margin):
-    """Transformer.evaluate -> greedy_decode on the non-fast _DecodeSession: per step three _lowrank products into row t of the K / V
+    """Transformer.evaluate -> greedy_decode on the non-fast decode._DecodeSession: per step three _lowrank products into row t of the K / V
     caches ((B, S, h d_k) and (B, S, h d_v): two row widths in model B) and _attend over t + 1 cached rows and over the 72 rows of each
     utterance's own memory -- four utterances, 40 steps, ids equal to oracle.refimpl.greedy_search; eager, recorded and replayed."""
     from oracle import refimpl as R
@@ -301,9 +301,9 @@ def test_greedy_search_matches_the_cpu_oracle(name, seed, margin):
     for rnd in range(3):
         model.evaluate(x.cuda(), lens, y, args, start_token=vocab.SOS_ID, max_steps=GREEDY_STEPS)
         assert torch.equal(model.last_greedy_ids.t().contiguous(), ref), rnd
-    keys = list(model.engine._decode_lists)
+    keys = model.engine.replay_greedy.keys()
     assert len(keys) == 1 and keys[0][-1] is False                                   # the session was not the `fast` one
-    assert not isinstance(model.engine._decode_lists[keys[0]], str)                  # ... and its steps were recorded and replayed
+    assert len(model.engine.replay_greedy.recorded(keys[0])) == 1                    # ... and its steps were recorded and replayed
 
 
 # (model, seed) of R.synth_batch(seed, 4, 288, 6, 64, True) and the batch's smallest decision margin on the CPU oracle at W = 3
@@ -352,6 +352,6 @@ def test_beam_searches_match_the_cpu_oracle(name, seed, margin):
     close(hst)
     assert batch() == dev and batch() == dev                                         # recorded and replayed command lists
     assert host() == hst
-    assert eng._beamb_lists and all(key[-1] is False for key in eng._beamb_lists)    # neither session was the `fast` one
-    assert eng._beam_lists and all(key[-1] is False for key in eng._beam_lists)
-    assert any(ent['lists'] for ent in eng._beamb_lists.values())
+    for replay in (eng.replay_beam_batch, eng.replay_beam):                          # neither session was the `fast` one
+        assert replay.keys() and all(key[-1] is False for key in replay.keys())
+    assert eng.replay_beam_batch.recorded()

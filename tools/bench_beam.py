@@ -71,7 +71,7 @@ def main():
                 fn()
                 torch.cuda.synchronize()
                 times[name].append(k / (time.perf_counter() - t0))
-        lists = [cl for ent in eng._beamb_lists.values() for cl in ent['lists'].values()]
+        lists = eng.replay_beam_batch.recorded()
         per_pos = max(cl.n for cl in lists) / eng.BEAM_POLL if lists else None
         positions = [max(len(s) for s, _ in u) - 1 if u else 0 for u in d]
         print(json.dumps(dict(params=params, host_utt_per_s=[round(v, 2) for v in times['host']],
