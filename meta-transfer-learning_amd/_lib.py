@@ -332,19 +332,26 @@ class Recorder:
 
 
 class Replay:
-    """Eager, then recorded, then replayed: the rule the decoders apply to a fixed sequence of library calls.  Under at most `capacity`
-    keys (everything the recorded addresses and arguments depend on; the oldest inserted key is evicted first) any number of units
-    (a whole greedy decode, one position, one block of positions).  `run = replay.begin(eng, key)` once per search, then `run(unit, body)`:
+    """Eager, then recorded, then replayed: the rule the decoders and the trainer's meta-step schedules apply to a fixed sequence of
+    library calls.  Under at most `capacity` keys (everything the recorded addresses and arguments depend on; the oldest inserted key
+    is evicted first, with `lru` the least recently looked-up one) any number of units (a whole greedy decode, one position, one block
+    of positions, one task body).  `run = replay.begin(eng, key)` once per search, then `run(unit, body)`:
     body() runs eagerly at the unit's first sighting, at the second with eng.lib replaced by a Recorder, and from the third on the
     recorded CommandList runs in its place.  Recorded lists hold raw addresses: an entry made at another eng.scratch_epoch starts
     over, a list is kept only if the epoch did not move while it was recorded, and a search under which the epoch moves finishes
-    eagerly.  While eng.prof is set or eng.lib is a Recorder already, body() runs directly and nothing here changes."""
+    eagerly.  While eng.prof is set or eng.lib is a Recorder already, body() runs directly and nothing here changes.
+    run(..., inputs=(addresses), on_break=f): `inputs` are the current addresses of the pointer arguments that move between replays
+    (a lane's two input batches); the list remembers the ones it was recorded with and is re-pointed before it runs.  Inputs must be
+    told apart by address: where two coincide the body runs eagerly (and nothing is recorded).  on_break: CommandList.run."""
 
-    def __init__(self, capacity):
-        self.capacity, self._entries = int(capacity), {}
+    def __init__(self, capacity, lru=False):
+        self.capacity, self.lru, self._entries = int(capacity), bool(lru), {}
 
     def keys(self):
         return list(self._entries)
+
+    def clear(self):
+        self._entries.clear()
 
     def recorded(self, key=None):
         """the finished CommandLists of `key` (default: of every key)"""
@@ -360,14 +367,30 @@ class Replay:
                 self._entries.pop(key, None)
                 while len(self._entries) >= self.capacity:
                     self._entries.pop(next(iter(self._entries)))
-                ent = self._entries[key] = dict(epoch=eng.scratch_epoch, seen=set(), lists={})
+                ent = self._entries[key] = dict(epoch=eng.scratch_epoch, seen=set(), lists={}, at={})
+            elif self.lru:
+                self._entries[key] = self._entries.pop(key)
 
-        def run(unit, body):
+        def run(unit, body, inputs=None, on_break=None):
             if ent is None or bypass() or ent['epoch'] != eng.scratch_epoch:
                 body()
+            elif unit not in ent['seen']:
+                ent['seen'].add(unit)
+                body()
+            elif inputs is not None and len(set(inputs)) < len(inputs):
+                body()
             elif unit in ent['lists']:
-                ent['lists'][unit].run()
-            elif unit in ent['seen']:
+                cl, at = ent['lists'][unit], ent['at'][unit]
+                if inputs is not None and at != inputs:
+                    # through placeholder values (no device address is that small): two inputs may have swapped addresses
+                    moved = [(8 * (i + 1), old, new) for i, (old, new) in enumerate(zip(at, inputs)) if old != new]
+                    for tmp, old, _ in moved:
+                        cl.repoint(old, tmp)
+                    for tmp, _, new in moved:
+                        cl.repoint(tmp, new)
+                    ent['at'][unit] = tuple(inputs)
+                cl.run(on_break)
+            else:
                 cl, real = CommandList(), eng.lib
                 eng.lib = Recorder(real, cl)
                 try:
@@ -375,10 +398,7 @@ class Replay:
                 finally:
                     eng.lib = real
                 if ent['epoch'] == eng.scratch_epoch:
-                    ent['lists'][unit] = cl.finish()
-            else:
-                ent['seen'].add(unit)
-                body()
+                    ent['lists'][unit], ent['at'][unit] = cl.finish(), tuple(inputs or ())
         return run
 
 

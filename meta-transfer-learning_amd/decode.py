@@ -288,7 +288,7 @@ def greedy_decode(eng, theta, mem, B, T4, start_token, max_steps=300):
     # The ~64 launches of a step cost the host more (8 us each through ctypes) than the device (a decode was host-bound at 0.53 ms
     # per step): the calls of all steps are recorded once per (parameters, shapes, buffers) into ONE command list -- every address is
     # fixed: the session's buffers come from the pool by name and shape -- and replayed from C (_lib.Replay, as
-    # TransientTrainer._run_recorded does for a task body).
+    # the trainer's schedules do for a task body: metastep._run_tasks).
     key = (theta.data_ptr(), int(mem), B, T4, max_steps, ys.data_ptr(), eng.stream, ses.fast)
     eng.replay_greedy.begin(eng, key)(0, steps)
     return ys[1:]

@@ -296,7 +296,7 @@ class PassEngine:
         if t is None or t.numel() * 4 < nbytes:
             t = torch.empty((int(nbytes) + 3) // 4 + 1024, dtype=torch.float32, device=self.device)
             self.arena['_scratch'] = t
-            self.scratch_epoch += 1          # recorded command lists hold the old address: they are re-recorded (trainer._run_recorded)
+            self.scratch_epoch += 1          # recorded command lists hold the old address: their keys start over (_lib.Replay)
         return t.data_ptr()
 
     @property

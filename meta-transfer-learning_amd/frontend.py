@@ -559,7 +559,7 @@ class BatchFrontEnd:
 
     def __init__(self, sample_rate, normalize, device, consumer):
         """consumer: the stream on which the batches of `batch()` are read (default: the device's current stream at construction --
-        the stream on which TransientTrainer._batched_iteration copies device-resident inputs into its static buffers)."""
+        the stream on which metastep._stage_inputs copies device-resident inputs into its static buffers)."""
         self.sample_rate, self.normalize, self.device = sample_rate, normalize, torch.device(device)
         self.consumer = consumer if consumer is not None or self.device.type != 'cuda' else torch.cuda.current_stream(self.device)
         self.stream = None                                     # batch()'s own stream, made at its first call

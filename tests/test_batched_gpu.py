@@ -307,7 +307,7 @@ def test_task_batched_iteration_equals_per_task_lanes(name, clip, smoothing):
         assert torch.equal(G2, G1)
         for (l1, h1, g1), (l2, h2, g2) in zip(r1, r2):
             assert l1 == l2 and torch.equal(h1, h2) and torch.equal(g1, g2)
-    assert any(isinstance(v, dict) and k_[0] == 'batched' for k_, v in tr._cmdlists.items()), 'no command list was recorded'
+    assert any(k_[0] == 'batched' and tr.replay.recorded(k_) for k_ in tr.replay.keys()), 'no command list was recorded'
 
 
 def test_task_batched_iteration_with_dropout_is_deterministic():
@@ -356,7 +356,7 @@ def test_eight_tasks_at_north_star_shapes_three_schedules():
     inner = mtl_amd.FlatSGD(model, spec['lr'])
     model.zero_copy_grad()
     Gb, rb, trb, _ = _iteration(mtl_amd, model, vocab, args, tasks, val, 8, inner, True)
-    assert any(k_[0] == 'batched' for k_ in trb._cmdlists), 'the batched path did not run'
+    assert any(k_[0] == 'batched' for k_ in trb.replay.keys()), 'the batched path did not run'
     lanes = model.n_lanes
     res = {}
     for nl in (1, lanes):
@@ -483,7 +483,7 @@ def test_tasks_of_different_frame_counts_in_one_pass_equal_a_lane_per_task(name,
     for rnd in range(3):                                  # first sighting of the key (eager), recording, replay
         G2, r2, _, _ = _iteration(mtl_amd, model, vocab, args, tasks, val, n, inner, True, tr=tr)
         assert torch.equal(G2, G1)
-    assert any(isinstance(v, dict) and k_[0] == 'batched' for k_, v in tr._cmdlists.items()), 'no command list was recorded'
+    assert any(k_[0] == 'batched' and tr.replay.recorded(k_) for k_ in tr.replay.keys()), 'no command list was recorded'
     # the recorded list holds no frame count: other per-task counts under the same widest replay it -- bit for bit what a fresh trainer
     # enqueues call by call
     other = tuple(max(frames) if f == max(frames) else f - 3 for f in frames)
@@ -579,7 +579,7 @@ def test_a_lane_per_task_at_rounded_widths_equals_its_own_widths(name, frames, v
     fresh.pad_lanes, fresh.ragged_quantum = '1', 16
     G4, _, _, _ = _iteration(mtl_amd, model, vocab, args, tasks_b, val, n, inner, False, tr=fresh)
     assert torch.equal(G3, G4)
-    assert any(isinstance(v, dict) for v in wide._cmdlists.values()), 'no command list was recorded'
+    assert any(wide.replay.recorded(k_) for k_ in wide.replay.keys()), 'no command list was recorded'
 
 
 def test_stand_alone_passes_at_rounded_widths_match_the_oracle_at_their_own():

@@ -134,7 +134,7 @@ def test_ctc_meta_iteration_batched_equals_lanes_and_is_keyed_apart_from_ce():
         assert torch.equal(G2, G1)
         for (l1, h1, g1), (l2, h2, g2) in zip(r1, r2):
             assert (l1 == l2 or (np.isinf(l1) and np.isinf(l2))) and torch.equal(h1, h2) and torch.equal(g1, g2)
-    assert any(isinstance(v, dict) and k_[0] == 'batched' and 'ctc' in k_ for k_, v in tr._cmdlists.items()), 'no ctc command list was recorded'
+    assert any(k_[0] == 'batched' and 'ctc' in k_ and tr.replay.recorded(k_) for k_ in tr.replay.keys()), 'no ctc command list was recorded'
     # one trainer, the same shapes: ce lists and ctc lists never stand in for each other
     for sched in (True, False):
         one = mtl_amd.TransientTrainer()
@@ -147,7 +147,7 @@ def test_ctc_meta_iteration_batched_equals_lanes_and_is_keyed_apart_from_ce():
             seen[lt] = (G, r)
         assert not torch.equal(seen['ce'][0], seen['ctc'][0])
         assert all(np.isfinite(r[0]) for r in seen['ce'][1]) and seen['ce'][1][0][0] != seen['ctc'][1][0][0]
-        assert sum(isinstance(v, dict) for v in one._cmdlists.values()) >= 2
+        assert sum(bool(one.replay.recorded(k_)) for k_ in one.replay.keys()) >= 2
     assert torch.equal(seen['ctc'][0], G0)                         # (the last round ran the lanes)
 
 

@@ -397,6 +397,45 @@ def test_schedule_choice_for_batches_of_different_widths():
     assert tr._can_batch(model, [batch(2, 64), batch(2, 64)], val) and not tr._can_batch(model, [batch(2, 64), batch(2, 40)], val)
 
 
+def test_command_list_key_holds_the_address_of_every_tensor_the_task_program_bakes_in():
+    """metastep.command_list_key: the schedule's tag first, the scalars, then the address of every tensor -- a census buffer that was
+    re-allocated (or switched on / off), or another theta0 / g / theta' / G buffer, is another key; the same tensors are the same key."""
+    import mtl_amd  # noqa: F401
+    from mtl_amd.metastep import command_list_key
+    theta0, g, theta1, G, cen_a, cen_b = (torch.zeros(8) for _ in range(6))
+    other = torch.zeros(8)
+    scalars = ('ctc', 0, None, (2, 1, 161, 64), 3, 1e-2, False, 400.0, 0.0)
+    key = lambda *tensors: command_list_key('lanes', scalars, tensors)
+    base = key(theta0, g, theta1, G, cen_a)
+    assert base[0] == 'lanes' and 'ctc' in base and command_list_key('batched', scalars, (theta0,))[0] == 'batched'
+    assert base == key(theta0, g, theta1, G, cen_a) and hash(base) == hash(key(theta0, g, theta1, G, cen_a))
+    assert base == key(theta0, g, theta1, G, cen_a[:])                     # (a view at the same address)
+    assert len({base, key(theta0, g, theta1, G, cen_b), key(theta0, g, theta1, G, None), key(theta0, g, theta1, G, cen_a[4:])}) == 4
+    for i in range(4):                                                     # theta0, g, theta', G in turn
+        tensors = [theta0, g, theta1, G, cen_a]
+        tensors[i] = other
+        assert key(*tensors) != base, i
+    assert command_list_key('lanes', scalars[:-1] + (0.1,), (theta0, g, theta1, G, cen_a)) != base
+
+
+def test_trainer_keeps_a_read_only_view_of_its_replay_in_the_earlier_form():
+    """TransientTrainer._cmdlists: {key: 'warm' | dict(cl=list)} over trainer.replay, empty after clear()"""
+    import types
+    import mtl_amd
+    tr = mtl_amd.TransientTrainer()
+    eng = types.SimpleNamespace(lib=object(), prof=None, scratch_epoch=0)
+    assert not tr._cmdlists and tr.replay.lru and tr.replay.capacity == 64
+    tr.replay.begin(eng, ('batched', 'ce'))(0, lambda: None)
+    tr.replay.begin(eng, ('lanes', 'ce'))(0, lambda: None)
+    assert tr._cmdlists == {('batched', 'ce'): 'warm', ('lanes', 'ce'): 'warm'}
+    tr.replay.begin(eng, ('batched', 'ce'))(0, lambda: None)
+    view = tr._cmdlists
+    assert list(view) == [('lanes', 'ce'), ('batched', 'ce')] and view[('lanes', 'ce')] == 'warm'
+    assert view[('batched', 'ce')] == dict(cl=tr.replay.recorded(('batched', 'ce'))[0])
+    tr.replay.clear()
+    assert not tr._cmdlists and len(tr._cmdlists) == 0
+
+
 def test_environment_switches_are_the_documented_ones():
     """Every MTL_* variable the package reads is in INTEGRATION.md's table and is flipped by a test; nothing else is read (round 5 had
     58 of them, most left over from experiments that lost -- every one an untested configuration of a loop people run for days)."""

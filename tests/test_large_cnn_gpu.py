@@ -96,7 +96,7 @@ def test_command_lists_equal_the_eager_step_bitwise():
         assert torch.equal(G0, G1), rnd
         for (l0, h0, g0), (l1, h1, g1) in zip(r0, r1):
             assert l0 == l1 and torch.equal(h0, h1) and torch.equal(g0, g1)
-    assert any(isinstance(v, dict) and k_[0] == 'batched' for k_, v in tr._cmdlists.items()), 'no command list was recorded'
+    assert any(k_[0] == 'batched' and tr.replay.recorded(k_) for k_ in tr.replay.keys()), 'no command list was recorded'
     # ... and the lanes (one task per engine, single-task launches) give the batched step's G to the summation-order bar
     G2, r2, _, _ = _iteration(mtl_amd, model, vocab, args, tasks, val, n, inner, False)
     errs = _tensor_errs(model, G2, G0)

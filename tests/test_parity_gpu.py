@@ -670,7 +670,7 @@ def test_dropout_pass_matches_oracle_with_the_same_masks():
 
 @pytest.mark.parametrize('dropout', [0.0, 0.1])
 def test_command_list_replay_is_bitwise_equal_to_eager(dropout):
-    """The per-task body recorded into a command list and replayed by mtl_cmdlist_run (trainer._run_recorded, default on) must
+    """The per-task body recorded into a command list and replayed by mtl_cmdlist_run (the trainer's _lib.Replay, default on) must
     reproduce the eager meta-gradient bit for bit -- side-stream fork / join, re-pointed input batches and (with dropout) the
     per-pass Philox seeds read from device memory included -- also for batches it was not recorded on."""
     z, cfg, spec = gu.load('F0')
@@ -696,8 +696,8 @@ def test_command_list_replay_is_bitwise_equal_to_eager(dropout):
             outs.append((model._G.clone(), [(r.loss.clone(), r.hyp.clone()) for pair in reads for r in pair]))
         res[mode] = outs
         if mode:
-            recorded = [v for v in tr._cmdlists.values() if isinstance(v, dict)]
-            assert len(recorded) == min(model.n_lanes, 6) and all(v['cl'].n > 100 for v in recorded)      # one list per lane in use
+            recorded = tr.replay.recorded()
+            assert len(recorded) == min(model.n_lanes, 6) and all(cl.n > 100 for cl in recorded)      # one list per lane in use
     for (G0, r0), (G1, r1) in zip(res[False], res[True]):
         assert torch.equal(G0, G1)
         for (l0, h0), (l1, h1) in zip(r0, r1):

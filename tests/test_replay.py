@@ -1,5 +1,7 @@
 """_lib.Replay on the CPU: the eager / recorded / replayed rule of the decoders, with a stub engine (lib, prof, scratch_epoch) and
-bodies that make no recordable call -- an empty finished CommandList runs without a device."""
+bodies that make no recordable call -- an empty finished CommandList runs without a device.  Further down, what the trainer's
+schedules add to it (eviction of the least recently used key, inputs that move between replays, on_break, clear()), with a stub library
+handle that lets the Recorder log one call's real pointer arguments."""
 import pytest
 
 
@@ -179,3 +181,161 @@ def test_units_of_one_key_are_independent(built):
     assert isinstance(body4.libs[-1], L.Recorder) and len(rp.recorded('k')) == 2
     run(4, body4)
     assert body4.calls == 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what the trainer's schedules add: least-recently-used eviction, inputs that move between replays, on_break, clear()
+# ---------------------------------------------------------------------------------------------------------------------
+class _Handle:
+    """stands in for the ctypes handle: one recordable name, whose call does nothing and succeeds -- the Recorder then logs real
+    pointer arguments without a device"""
+
+    def mtl_cmdlist_opcode(self, name):
+        return 7 if name == b'mtl_axpy' else -1
+
+    def mtl_axpy(self, *args):
+        return 0
+
+
+class _Axpy:
+    """a body of one recordable call, mtl_axpy(stream, y, x, a, n), on the two addresses `at` holds at that moment"""
+
+    def __init__(self, eng):
+        self.eng, self.at, self.calls, self.libs = eng, None, 0, []
+
+    def __call__(self):
+        self.calls += 1
+        self.libs.append(self.eng.lib)
+        assert self.eng.lib.mtl_axpy(0x1000, self.at[0], self.at[1], 1.0, 4) == 0
+
+
+A, B, C, D = 0x7f0000010000, 0x7f0000020000, 0x7f0000030000, 0x7f0000040000
+
+
+@pytest.fixture
+def ran(built, monkeypatch):
+    """CommandList.run replaced by a note of (the pointer arguments y, x the list holds at that moment, the on_break it got)"""
+    log = []
+    monkeypatch.setattr(built._lib.CommandList, 'run', lambda self, on_break=None: log.append(
+        ([self.buf[i].a[j].p for i in range(self.n) for j in (1, 2)], on_break)))
+    return log
+
+
+def _moving(L, **kw):
+    eng = _Eng()
+    eng.lib = _Handle()
+    return eng, L.Replay(4, **kw), _Axpy(eng)
+
+
+def _sight_at(rp, eng, body, at, inputs='at', on_break=None, key='k'):
+    body.at = at
+    rp.begin(eng, key)(0, body, inputs=at if inputs == 'at' else inputs, on_break=on_break)
+
+
+@pytest.mark.parametrize('capacity', [2, 4])
+def test_with_lru_a_replayed_oldest_key_survives_the_next_insertion(built, capacity):
+    L = built._lib
+    eng, rp = _Eng(), L.Replay(capacity, lru=True)
+    body = _Body(eng)
+    keys = ['k%d' % i for i in range(capacity)]
+    for k in keys:
+        _sight(rp, eng, k, body)
+        _sight(rp, eng, k, body)
+    assert rp.keys() == keys
+    calls = body.calls
+    _sight(rp, eng, keys[0], body)                           # a replay of the oldest key makes it the youngest
+    assert body.calls == calls and rp.keys() == keys[1:] + [keys[0]]
+    _sight(rp, eng, 'new', body)
+    assert rp.keys() == keys[2:] + [keys[0], 'new'] and rp.recorded(keys[1]) == [] and len(rp.recorded(keys[0])) == 1
+    _sight(rp, eng, keys[0], body)                           # ... and is still replayed
+    assert body.calls == calls + 1
+
+
+def test_inputs_that_change_between_replays_are_repointed(built, ran):
+    eng, rp, body = _moving(built._lib)
+    _sight_at(rp, eng, body, (A, B))
+    _sight_at(rp, eng, body, (A, B))
+    assert body.calls == 2 and isinstance(body.libs[1], built._lib.Recorder) and ran == []
+    (cl,) = rp.recorded('k')
+    assert cl.n == 1 and cl.buf[0].op == 7 and [cl.buf[0].a[j].p for j in range(3)] == [0x1000, A, B]
+    _sight_at(rp, eng, body, (A, B))                         # the same addresses: as recorded
+    _sight_at(rp, eng, body, (C, D))                         # both move
+    _sight_at(rp, eng, body, (C, A))                         # one moves, onto an address the other once had
+    _sight_at(rp, eng, body, (C, A))
+    assert body.calls == 2 and [r[0] for r in ran] == [[A, B], [C, D], [C, A], [C, A]]
+    assert cl.buf[0].a[0].p == 0x1000                        # (an argument that is no input stays)
+
+
+def test_two_inputs_that_swap_addresses_end_up_swapped(built, ran):
+    eng, rp, body = _moving(built._lib)
+    for _ in range(3):
+        _sight_at(rp, eng, body, (A, B))
+    _sight_at(rp, eng, body, (B, A))
+    _sight_at(rp, eng, body, (A, B))
+    assert body.calls == 2 and [r[0] for r in ran] == [[A, B], [B, A], [A, B]]
+
+
+def test_three_inputs_rotate_through_each_others_addresses(built, ran):
+    L = built._lib
+    eng = _Eng()
+    eng.lib = _Handle()
+    rp, at = L.Replay(4), [A, B, C]
+
+    def body():                                              # two calls: (y, x) = (in0, in1), (in2, in0)
+        assert eng.lib.mtl_axpy(0x1000, at[0], at[1], 1.0, 4) == 0 and eng.lib.mtl_axpy(0x1000, at[2], at[0], 1.0, 4) == 0
+    for now in ([A, B, C], [A, B, C], [B, C, A], [C, A, B], [A, B, D]):
+        at[:] = now
+        rp.begin(eng, 'k')(0, body, inputs=tuple(at))
+    assert [r[0] for r in ran] == [[B, C, A, B], [C, A, B, C], [A, B, D, A]]
+
+
+def test_an_input_address_that_is_no_argument_of_the_list_raises(built, ran):
+    eng, rp, body = _moving(built._lib)
+    for _ in range(2):
+        _sight_at(rp, eng, body, (A, B), inputs=(A, C))      # C is declared as an input, but the body never passes it
+    with pytest.raises(KeyError):
+        _sight_at(rp, eng, body, (A, B), inputs=(A, D))
+    assert ran == []
+
+
+def test_inputs_that_coincide_at_the_recording_sighting_run_eagerly_and_keep_no_list(built, ran):
+    L = built._lib
+    eng, rp, body = _moving(L)
+    real = eng.lib
+    _sight_at(rp, eng, body, (A, B))
+    _sight_at(rp, eng, body, (A, A))                         # the second sighting would record: the inputs cannot be told apart
+    assert body.calls == 2 and body.libs == [real, real] and rp.recorded() == [] and rp.keys() == ['k']
+    _sight_at(rp, eng, body, (C, D))                         # the next sighting with distinct inputs records
+    assert body.calls == 3 and isinstance(body.libs[2], L.Recorder) and len(rp.recorded('k')) == 1 and eng.lib is real
+    _sight_at(rp, eng, body, (A, B))
+    assert body.calls == 3 and [r[0] for r in ran] == [[A, B]]
+    _sight_at(rp, eng, body, (D, D))                         # ... and coinciding inputs never reach a recorded list
+    assert body.calls == 4 and body.libs[3] is real and len(ran) == 1
+    _sight_at(rp, eng, body, (C, D))
+    assert body.calls == 4 and [r[0] for r in ran] == [[A, B], [C, D]]
+
+
+def test_on_break_reaches_the_replay(built, ran):
+    eng, rp, body = _moving(built._lib)
+    hook = lambda tag: None
+    for _ in range(3):
+        _sight_at(rp, eng, body, (A, B), on_break=hook)
+    _sight_at(rp, eng, body, (A, B))
+    assert [r[1] for r in ran] == [hook, None]
+    rp.begin(eng, 'static')(0, body)                         # (inputs=None: nothing moves)
+    rp.begin(eng, 'static')(0, body)
+    rp.begin(eng, 'static')(0, body, on_break=hook)
+    assert ran[-1] == ([A, B], hook)
+
+
+@pytest.mark.parametrize('lru', [False, True])
+def test_clear_empties_keys_and_recorded(built, ran, lru):
+    eng, rp, body = _moving(built._lib, lru=lru)
+    for key in ('k', 'm'):
+        for _ in range(2):
+            _sight_at(rp, eng, body, (A, B), key=key)
+    assert rp.keys() == ['k', 'm'] and len(rp.recorded()) == 2
+    rp.clear()
+    assert rp.keys() == [] and rp.recorded() == [] and rp.recorded('k') == []
+    _sight_at(rp, eng, body, (A, B))                         # a cleared key is at its first sighting again
+    assert body.calls == 5 and body.libs[-1] is eng.lib and rp.recorded() == []

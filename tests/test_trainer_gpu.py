@@ -350,7 +350,7 @@ def test_h2_range_guard_fires_on_a_loud_and_a_quiet_sample_and_moves_to_the_exac
     cen = tr.h2_census
     print('census:', {k: ('%.2f' % v[0], '%.2f' % v[1]) for k, v in cen.items()})
     assert cen['conv0 out'][1] > 0.3 and cen['pool2'][1] > 0.3           # the quiet sample's half of the non-zero elements
-    assert all(e.conv_mode == 'x3' and not e.conv_h2 for e in model.engines) and not tr._cmdlists
+    assert all(e.conv_mode == 'x3' and not e.conv_h2 for e in model.engines) and not tr.replay.keys()
     model.pass_forward(x.cuda(), lens, y)
     p2['x3'] = model.engine.arena['p2'].clone()
     # the exact split is the yardstick (its parity with the oracle: the whole-pass check at the end): under h2 the LOUD sample's conv
@@ -368,6 +368,36 @@ def test_h2_range_guard_fires_on_a_loud_and_a_quiet_sample_and_moves_to_the_exac
     for e in model.engines:
         e.conv_mode, e.conv_x3, e.conv_h2 = 'x3', True, False
     _pass_parity(model, oracle, batch, model.flat_parameters, 'loud / quiet pair on the exact split')
+
+
+def test_h2_census_counts_into_the_reallocated_buffer_when_the_lanes_replay():
+    """The census counter buffer has a row per lane or local task and is re-allocated when an iteration brings more local tasks than any
+    before it; the lanes and their shapes can stay the same across that.  Its address is part of every command-list key
+    (metastep.command_list_key), so the lists recorded against the old allocation are not replayed: after three iterations with
+    n_lanes tasks (eager, recorded, replayed) and one with 2 n_lanes tasks, the census of the command-list trainer equals the eager
+    trainer's, counter for counter (integers; eager and replay are bit-equal)."""
+    z, cfg, spec = gu.load('F0')
+    mtl_amd, args, vocab, _ = make(cfg, spec)
+    as5 = lambda b: (b[0].cuda(), b[1], None, b[2], None)
+    val = as5(mtl_amd.synth_batch(77, 2, 64, 8, cfg['vocab_size']))
+    census = {}
+    for mode in (True, False):
+        torch.manual_seed(123456)
+        model = mtl_amd.init_transformer_model(args, vocab, r=cfg['r']).cuda()
+        inner, outer = mtl_amd.FlatSGD(model, spec['lr']), mtl_amd.FlatAdam(model, spec['meta_lr'])
+        model.zero_copy_grad()
+        tr = mtl_amd.TransientTrainer()
+        tr.batch_tasks, tr.pipeline_depth, tr.h2_check_every, tr.use_cmdlists = False, 0, 1, mode
+        n = model.n_lanes
+        for it, nt in enumerate((n, n, n, 2 * n)):
+            tasks = [as5(mtl_amd.synth_batch(100 * it + i, 2, 64, 8, cfg['vocab_size'])) for i in range(nt)]
+            tr.enqueue_iteration(model, vocab, tasks, val, nt, inner, outer, args).result()
+            assert tr.last_schedule == 'lanes'
+        assert tr._h2_buf.shape[0] == 2 * n and all(e.conv_h2 for e in model.engines)
+        if mode:
+            assert len(tr.replay.recorded()) >= n        # (the lanes' lists were recorded, and replayed on the third iteration)
+        census[mode] = tr.h2_census
+    assert census[True] and census[True] == census[False], (census[True], census[False])
 
 
 def test_rccl_collective_path_executes():
@@ -435,7 +465,7 @@ def test_host_one_iteration_ahead_is_bitwise_equal(capsys):
 @pytest.mark.parametrize('ragged', [False, True])
 def test_uploads_on_their_own_stream_are_bitwise_equal(ragged):
     """Batches handed over in (pinned) host memory go up on a separate stream into alternating input sets, one iteration ahead of
-    the kernels (TransientTrainer._batched_iteration, transient_trainer.py:182-184,210-212 are inside the reference's span): theta and
+    the kernels (metastep._stage_inputs, transient_trainer.py:182-184,210-212 are inside the reference's span): theta and
     the per-iteration results after 6 pipelined iterations equal those of the in-stream upload (MTL_OVERLAP_UPLOADS=0 behaviour) and
     those of device-resident inputs, bit for bit -- also across the eager / recording / replay transitions of the command list.
     ragged: every batch at a width of its own, new ones every iteration (a batch lands contiguously at the front of its slab of the
@@ -500,7 +530,7 @@ def test_variable_length_batches_keep_the_buffer_pool_and_the_command_lists_boun
         peak = max(peak, max(e._pool_bytes for e in model.engines))
     assert eng.scratch_epoch > epochs, 'nothing was evicted'
     assert peak < 6 * one_pass, (peak, one_pass)         # without trimming: ~13 distinct shapes' worth
-    assert len(tr._cmdlists) <= 64 and len(eng._stage) <= 64 + 4
+    assert len(tr.replay.keys()) <= 64 and len(eng._stage) <= 64 + 4
     again = iteration(64, 8, 500)
     assert torch.equal(first, again)
 

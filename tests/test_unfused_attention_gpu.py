@@ -272,8 +272,8 @@ def test_meta_iteration_on_lanes_against_live_oracle(name):
         trainer.meta_iteration(model, vocab, tasks, vb, n, inner, None, args)
         torch.cuda.synchronize()
         assert trainer.last_schedule == 'lanes' and torch.equal(model._G, G0), rnd
-    recorded = [v for v in trainer._cmdlists.values() if isinstance(v, dict)]
-    assert len(recorded) == n and all(v['cl'].n > 100 for v in recorded)             # one list per lane, and it was replayed
+    recorded = trainer.replay.recorded()
+    assert len(recorded) == n and all(cl.n > 100 for cl in recorded)             # one list per lane, and it was replayed
 
 
 # (model, seed) of R.synth_batch(seed, 4, 288, 6, 64, True) and the smallest top-2 gap of the oracle's log-probabilities over the 4 rows

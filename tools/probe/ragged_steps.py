@@ -79,7 +79,7 @@ def main():
     print(json.dumps(dict(mode=a.mode, ms_per_step=round(dt / a.steps * 1e3, 2), meta_steps_per_s=round(a.steps / dt, 2),
                           frames_per_step=frames // a.steps, us_per_kiloframe=round(dt / frames * 1e9, 1),
                           host_enqueue_ms=dict(mean=round(sum(host[4:]) / len(host[4:]), 1), max=round(max(host[4:]), 1)),
-                          pool_gb=round(sum(e._pool_bytes for e in model.engines) / 2 ** 30, 2), cmdlists=len(getattr(trainer, '_cmdlists', {})),
+                          pool_gb=round(sum(e._pool_bytes for e in model.engines) / 2 ** 30, 2), cmdlists=len(trainer.replay.keys()),
                           mem_reserved_gb=round(torch.cuda.memory_reserved(dev) / 2 ** 30, 1), host_rss_gb=round(__import__('psutil').Process().memory_info().rss / 2 ** 30, 2),
                           allocator_retries=torch.cuda.memory_stats(dev).get('num_alloc_retries', 0), account_gb=round(eng.account['bytes'] / 2 ** 30, 1), schedule=trainer.last_schedule, loss=float(last[0]))))
 
