@@ -1069,13 +1069,14 @@ void conv3x3_x3h_kernel(ConvX3P p) {
     // registers across the matrix loop); (b) the epilogue addresses every access as scalar base + one 32-bit lane offset, with the lane
     // terms re-derived from the lane index inside the epilogue (SLIM_FWD: the ReLU / pool forms, SLIM_DG: the gated form).
     // SLIM_HALO: the halo waves keep their validity bits in one register and re-derive the elements' lane terms at the fetch and at
-    // the commit, and (SLIM_H32) fetch a pooled source with 32-bit offsets (launcher guard of its own).  Only the data gradients, whose
-    // un-pooling halo waves otherwise spill (conv7's: 56 bytes): the re-derivation sits in the commit, between the two barriers of a
-    // halo swap, and cost the forwards 5 % (their halo waves carry no arg-max codes and fit without it).
+    // the commit; SLIM_H32: a pooled source is fetched with 32-bit offsets (launcher guard of its own).  Only the dense 64-channel-wave
+    // data gradient: the re-derivation sits in the commit, between the two barriers of a halo swap, and cost the forwards 5 %.  The
+    // un-pooling forms needed it while they gathered per un-pooled position (14 x (float4 + codes) per thread: conv7's halo waves
+    // spilled 56 bytes without it); gathering per pooled element (5 per thread) they compile without scratch and without it.
     constexpr bool SLIM_FWD = !WIDE && x3h_slim_fwd<BN, G, UNPOOL, EPI, NP, WN>();
     constexpr bool SLIM_H32 = WN == 1 && EPI == EPI_DGRAD;
     constexpr bool SLIM_DG = SLIM_H32 || (!WIDE && x3h_slim_dg128<BN, G, UNPOOL, EPI, NP, WN>());
-    constexpr bool SLIM_HALO = SLIM_DG;
+    constexpr bool SLIM_HALO = SLIM_DG && !UNPOOL;
     constexpr bool SLIM = SLIM_DG || SLIM_FWD;
     constexpr int CW = 2 * WN;                                      // consumer waves per 8 x 16 sub-tile
     constexpr int WTM = 64, WTN = BN / WN, TM = WTM / 32, TN = WTN / 32;
@@ -1111,42 +1112,57 @@ void conv3x3_x3h_kernel(ConvX3P p) {
                 sx = pow2_scale(x3_amax_read<SLIM>(p.amax_in + tk * p.sAmaxIn));
             }
         };
-        float4 hv[XH_NVA];
-        uchar4 ha[XH_NVA];
-        unsigned hm[SLIM_HALO ? 1 : XH_NVA];        // SLIM_HALO: the validity bits of all elements in hm[0] (the window position is re-derived at the commit)
+        // UNPOOL: an element is a POOLED source element -- pooling window (wr, wc) of the (4 G + 2) x 10 that the halo touches (tile origins
+        // are even: halo row ht lies in window (ht + 1) >> 1 at row parity (ht + 1) & 1, columns alike), channels c4 .. c4 + 3 -- fetched
+        // and split once and committed to the up to four halo pixels of its window (edge windows have one row / column inside the halo).
+        constexpr int XW_WF = XH_HF / 2 + 1, XW_NW = (XH_HT / 2 + 1) * XW_WF;     // windows along F; windows per halo
+        constexpr int XW_NVA = (XW_NW * 8 + NHALO - 1) / NHALO;                  // G = 2: 800 elements, at most 5 per thread (un-pooled: 2592, 14)
+        constexpr int NVA = UNPOOL ? XW_NVA : XH_NVA;
+        float4 hv[NVA];
+        uchar4 ha[NVA];
+        unsigned hm[SLIM_HALO || UNPOOL ? 1 : XH_NVA];   // SLIM_HALO / UNPOOL: the validity bits of all elements in hm[0]
         auto fetch_halo = [&](int q) {          // stage q: channels c*32 .. +31 of the halo pixels of its tile
             const int j = q / cch, c = q - j * cch;
             const X3Tile tl = x3_tile<G>(p, blockIdx.x + j * gridDim.x, cur_halo);
             int pt = ptid;                      // (SLIM_HALO: the elements' lane terms are derived here, not kept -- spilled -- from the prologue)
             if constexpr (SLIM_HALO) asm volatile("" : "+v"(pt));
+            if constexpr (UNPOOL) {
+                // A window inside Tp x Fp has all four of its positions inside T x F (Tp = T / 2, Fp = F / 2: the C ABI derives them),
+                // and a position outside every such window -- beyond the image, or the last row / column of an odd extent -- is zero.
+                const int tw0 = (tl.t0 >> 1) - 1, fw0 = (tl.f0 >> 1) - 1;
+#pragma unroll
+                for (int i = 0; i < XW_NVA; ++i) {
+                    const int e = pt + i * NHALO;
+                    const int w = min(e >> 3, XW_NW - 1), c4 = (e & 7) * 4;
+                    const int wr = w / XW_WF, wc = w - wr * XW_WF;
+                    const int tp = tw0 + wr, fp = fw0 + wc;
+                    const bool ok = (e >> 3) < XW_NW && (unsigned)tp < (unsigned)Tp && (unsigned)fp < (unsigned)Fp;
+                    const int tpc = max(min(tp, Tp - 1), 0), fpc = max(min(fp, Fp - 1), 0);
+                    if constexpr (SLIM_H32) {   // scalar base of the (sample, chunk) + one 32-bit offset for both loads: no 64-bit address pair per element
+                        const long sbase = (long)__builtin_amdgcn_readfirstlane(tl.b) * Tp * Fp * Cin + c * BK;
+                        const unsigned o = (unsigned)((tpc * Fp + fpc) * Cin + c4);
+                        ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + sbase + o);
+                        hv[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.x + sbase) + o * 4u);
+                    } else {
+                        const long o = (((long)tl.b * Tp + tpc) * Fp + fpc) * Cin + c * BK + c4;
+                        ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + o);
+                        hv[i] = *reinterpret_cast<const float4*>(p.x + o);
+                    }
+                    hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
+                }
+                return;
+            }
 #pragma unroll
             for (int i = 0; i < XH_NVA; ++i) {
                 const int e = pt + i * NHALO;
                 const int hp = min(e >> 3, XH_NPIX - 1), c4 = (e & 7) * 4;
                 const int ht = hp / XH_HF, hf = hp - ht * XH_HF;
                 const int ts = tl.t0 + ht - 1, fs = tl.f0 + hf - 1;
-                bool ok = (e >> 3) < XH_NPIX && (unsigned)ts < (unsigned)T && (unsigned)fs < (unsigned)F;
+                const bool ok = (e >> 3) < XH_NPIX && (unsigned)ts < (unsigned)T && (unsigned)fs < (unsigned)F;
                 const int tc = min(max(ts, 0), T - 1), fc = min(max(fs, 0), F - 1);
-                if (!UNPOOL) {
-                    hv[i] = *reinterpret_cast<const float4*>(p.x + (((long)tl.b * T + tc) * F + fc) * Cin + c * BK + c4);
-                    if constexpr (SLIM_HALO) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
-                    else hm[i] = ok ? 1u : 0u;
-                } else {
-                    const int tp = tc >> 1, fp = fc >> 1;
-                    ok = ok && tp < Tp && fp < Fp;
-                    if constexpr (SLIM_H32) {   // scalar base of the (sample, chunk) + one 32-bit offset for both loads: no 64-bit address pair per element
-                        const long sbase = (long)__builtin_amdgcn_readfirstlane(tl.b) * Tp * Fp * Cin + c * BK;
-                        const unsigned o = (unsigned)((min(tp, Tp - 1) * Fp + min(fp, Fp - 1)) * Cin + c4);
-                        ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + sbase + o);
-                        hv[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.x + sbase) + o * 4u);
-                    } else {
-                    const long o = (((long)tl.b * Tp + min(tp, Tp - 1)) * Fp + min(fp, Fp - 1)) * Cin + c * BK + c4;
-                    ha[i] = *reinterpret_cast<const uchar4*>(p.am_in + o);
-                    hv[i] = *reinterpret_cast<const float4*>(p.x + o);
-                    }
-                    if constexpr (SLIM_HALO) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
-                    else hm[i] = (ok ? 1u : 0u) | ((unsigned)(((fs & 1) << 1) | (ts & 1)) << 1);
-                }
+                hv[i] = *reinterpret_cast<const float4*>(p.x + (((long)tl.b * T + tc) * F + fc) * Cin + c * BK + c4);
+                if constexpr (SLIM_HALO) hm[0] = i ? hm[0] | ((ok ? 1u : 0u) << i) : (ok ? 1u : 0u);
+                else hm[i] = ok ? 1u : 0u;
             }
         };
         // (Splitting ahead of the swap barrier so that only the ds_writes sit between the two barriers was tried: the 84
@@ -1154,23 +1170,36 @@ void conv3x3_x3h_kernel(ConvX3P p) {
         auto commit_halo = [&]() {
             int pt = ptid;
             if constexpr (SLIM_HALO) asm volatile("" : "+v"(pt));
+            if constexpr (UNPOOL) {
+#pragma unroll
+                for (int i = 0; i < XW_NVA; ++i) {
+                    const int e = pt + i * NHALO;
+                    if ((e >> 3) >= XW_NW) continue;
+                    const int wr = (e >> 3) / XW_WF, wc = (e >> 3) - wr * XW_WF;
+                    uint2 pc[NP];
+                    split_x4<NP>(hv[i], sx, pc);                                  // once per pooled value: a position takes the piece words or zero
+                    const uchar4 a = (hm[0] >> i) & 1u ? ha[i] : make_uchar4(255, 255, 255, 255);      // (no window there: no position matches)
+                    unsigned char* dst = smA + ((2 * wr - 1) * XH_HF + 2 * wc - 1) * X3_ROWB + (e & 7) * 8;    // halo pixel of position 0
+#pragma unroll
+                    for (int pos = 0; pos < 4; ++pos) {                           // pos = ((f & 1) << 1) | (t & 1): what the arg-max code names
+                        const int dr = pos & 1, dc = pos >> 1;
+                        if ((dr ? wr < XH_HT / 2 : wr > 0) && (dc ? wc < XW_WF - 1 : wc > 0)) {        // the position lies inside the halo
+                            const unsigned m0 = (a.x == pos ? 0xffffu : 0u) | (a.y == pos ? 0xffff0000u : 0u);
+                            const unsigned m1 = (a.z == pos ? 0xffffu : 0u) | (a.w == pos ? 0xffff0000u : 0u);
+#pragma unroll
+                            for (int q = 0; q < NP; ++q)
+                                *reinterpret_cast<uint2*>(dst + (dr * XH_HF + dc) * X3_ROWB + q * XH_APLANE) = make_uint2(pc[q].x & m0, pc[q].y & m1);
+                        }
+                    }
+                }
+                return;
+            }
 #pragma unroll
             for (int i = 0; i < XH_NVA; ++i) {
                 const int e = pt + i * NHALO;
                 if ((e >> 3) >= XH_NPIX) continue;
-                float4 v = hv[i];
                 const bool ok = SLIM_HALO ? (hm[0] >> i) & 1u : hm[i] & 1u;
-                if (!UNPOOL) {
-                    v = mask4(v, ok ? 15u : 0u);
-                } else {
-                    // (tile origins are even: the parities of ts = t0 + ht - 1 and fs = f0 + hf - 1 are those of ht + 1 and hf + 1)
-                    const int ht_ = (e >> 3) / XH_HF, hf_ = (e >> 3) - ht_ * XH_HF;
-                    const unsigned sub = SLIM_HALO ? (unsigned)((((hf_ + 1) & 1) << 1) | ((ht_ + 1) & 1)) : hm[SLIM_HALO ? 0 : i] >> 1;
-                    v.x = (ok && ha[i].x == sub) ? v.x : 0.f;
-                    v.y = (ok && ha[i].y == sub) ? v.y : 0.f;
-                    v.z = (ok && ha[i].z == sub) ? v.z : 0.f;
-                    v.w = (ok && ha[i].w == sub) ? v.w : 0.f;
-                }
+                const float4 v = mask4(hv[i], ok ? 15u : 0u);
                 uint2 pc[NP];
                 split_x4<NP>(v, sx, pc);
                 unsigned char* dst = smA + (e >> 3) * X3_ROWB + (e & 7) * 8;
@@ -2881,15 +2910,21 @@ __global__ __launch_bounds__(256) void conv_dgrad_edge_kernel(ConvX3P p) {
         for (int j = 0; j < 8; ++j) Ws[(kw * K + kc * 32 + kk0 + j) * N + n] = v[j] * inv_sw;
     }
     const int fs = F - 2, fp = fs >> 1;
-    for (int e = tid; e < (EDGE_PIX + 2) * K; e += 256) {
-        const int r = e / K, k = e - r * K, ts = t0 + r - 1, tp = ts >> 1;
+    // gathered per POOLED element, as the halo waves of the matrix kernel do: t0 is even, so rows t0 - 1 .. t0 + EDGE_PIX (r = 0 .. EDGE_PIX + 1)
+    // lie in EDGE_PIX / 2 + 2 window rows, row r in window (r + 1) >> 1 at parity (r + 1) & 1; a window row inside Tp has both its rows inside T
+    static_assert(EDGE_PIX % 2 == 0, "even row origins");
+    for (int e = tid; e < (EDGE_PIX / 2 + 2) * K; e += 256) {
+        const int wr = e / K, k = e - wr * K, tp = (t0 >> 1) - 1 + wr;
         float v = 0.f;
-        if (ts >= 0 && ts < T && tp < Tp && fp < Fp) {
+        unsigned code = 255u;                                                      // (no window: neither row matches)
+        if (tp >= 0 && tp < Tp && fp < Fp) {
             const long o = (((long)b * Tp + tp) * Fp + fp) * K + k;
-            const unsigned sub = (unsigned)(((fs & 1) << 1) | (ts & 1));
-            v = p.am_in[o] == sub ? p.x[o] : 0.f;
+            v = p.x[o];
+            code = p.am_in[o];
         }
-        src[e] = v;
+        const unsigned sub = (unsigned)((fs & 1) << 1);
+        if (wr > 0) src[(2 * wr - 1) * K + k] = code == sub ? v : 0.f;
+        if (wr <= EDGE_PIX / 2) src[2 * wr * K + k] = code == (sub | 1u) ? v : 0.f;
     }
     __syncthreads();
     constexpr int PPG = EDGE_PIX / 4;                                              // 4 waves: wave g owns rows [g PPG, (g + 1) PPG), lane = n
