@@ -340,6 +340,18 @@ int mtl_attn_bwd(void* stream, const float* q, const float* k, const float* v, i
                  float pscale, const float* O, const float* dO, int ldo, const float* lse, float* delta, float* dq, float* dk_,
                  float* dv_, int lddq, int lddk, int lddv);
 
+/* ---- the middle of the factorized feed-forward block (--is-factorized; modules/common_layers.py:134-158) as one streamed kernel
+ * (csrc/mtl_ffn_lr.hip):  h = relu(a . B1^T + b1),  c = h . A2^T  with a (rows x r, row stride lda) the output of linear_1_a,
+ * B1 = linear_1_b.weight (inner x r), b1 its bias (inner), A2 = linear_2_a.weight (r x inner), c (rows x r, row stride ldc) the input
+ * of linear_2_b.  h (nullable; rows x inner, dense) receives the post-ReLU activation for the backward; c is bitwise the same with
+ * and without it.  `rows` is per task: task t < tasks reads a + t * sAt, the three weights + t * sWt floats (0: all tasks share
+ * them), and writes h + t * sHt, c + t * sCt.  Any rows >= 1; r a multiple of 4 up to 128 and inner a multiple of 4
+ * (mtl_ffn_lr_mid_supported; MTL_EINVAL otherwise); a, B1, A2 16-byte aligned, lda / sAt / sWt multiples of 4.  Exact bf16 triples,
+ * six MFMAs per block product, fixed summation order (bitwise reproducible), no atomics, no workspace. */
+int mtl_ffn_lr_mid_supported(int r, int inner);
+int mtl_ffn_lr_mid_fwd(void* stream, const float* a, int lda, const float* B1, const float* b1, const float* A2, float* h, float* c,
+                       int ldc, int rows, int r, int inner, int tasks, long sAt, long sWt, long sHt, long sCt);
+
 /* ---- embedding + positional encoding: modules/decoder.py:96 ------------------------------------------- */
 int mtl_embed_pe_fwd(void* stream, const long* ids, const float* table, const float* pe, float* out, int rows, int T, int d,
                      const unsigned char* mask /*nullable: dropout keep-mask*/, float mscale);

@@ -178,7 +178,12 @@ class Front:
         self.dims = [(B,) + TF[r.lvl] + (r.cin, r.cout) for r in self.layers]  # by Layer.i
         self.ad = _ADAPTERS[self.mode]
         self.d, self.d_in, self.Me = eng.hp.d, eng.hp.d_in, B * TF[2][0]        # (Me: encoder rows per task)
-        self.wp_strides = (AMAX_STRIDE, self.d * self.d_in) if self.sP else (0, 0)      # bound / weight of the next task's parameter set
+        # --is-factorized: the input Linear is the pair input_linear_a (d_in -> r, no bias: stage A, the dense Linear's arithmetic at
+        # n1 = r outputs) and input_linear_b (r -> d, bias: stage B, an ordinary engine product)
+        self.fz = eng.factorized
+        self.n1 = eng.hp.r if self.fz else self.d
+        self.w_in = 'encoder.input_linear_a.weight' if self.fz else 'encoder.input_linear.weight'
+        self.wp_strides = (AMAX_STRIDE, self.n1 * self.d_in) if self.sP else (0, 0)     # bound / weight of the next task's parameter set
         P, sP, off = S['theta'].data_ptr(), self.sP, eng.L.off                   # (no closure below refers to self: a Front is freed with its pass)
         self.o = lambda n, t=None: P + 4 * (off(n) + (t or 0) * sP)             # task t's parameter / its gradient; None: the stack's base
         self.g = lambda n, t=None: G + 4 * (off(n) + (t or 0) * sG)
@@ -251,29 +256,40 @@ class Front:
                     ad.fwd(self, r, t)
         self.census(('y1', 'p1', 'y5', 'p2'))
         # wp_in: the input Linear's weight with its 5120 (2560) inputs in p2's (bin, channel) order; max|w| rides along; a theta' stack in one launch
-        wp = eng.buf('wp_in', (self.ntw, self.d, self.d_in))
-        check(self.lib.mtl_permute_hc_tb(self.st, self.o('encoder.input_linear.weight'), wp.data_ptr(), self.d, self.c_out, self.TF[2][1], 0,
-                                         self.am(SLOT['wp']), self.ntw, self.sP, self.d * self.d_in, AMAX_STRIDE), 'permute')
+        wp = eng.buf('wp_in', (self.ntw, self.n1, self.d_in))
+        check(self.lib.mtl_permute_hc_tb(self.st, self.o(self.w_in), wp.data_ptr(), self.n1, self.c_out, self.TF[2][1], 0,
+                                         self.am(SLOT['wp']), self.ntw, self.sP, self.n1 * self.d_in, AMAX_STRIDE), 'permute')
 
     def linear_fwd(self):
         """e0 = p2 . wp^T + b: with the h2 convolutions on two fp16 pieces (one task-batched launch on the tile engine of
         mtl_gemm_x3.hip, per-task bounds by stride), else on the product engines' own routing"""
         eng, nt, Me, d, d_in, (s_am, s_w) = self.eng, self.nt, self.Me, self.d, self.d_in, self.wp_strides
         e0, p2, wp = eng.buf('e0', (nt * Me, d)), self.A['p2'], self.A['wp_in']
+        n1, ea = self.n1, (eng.buf('e0a', (nt * Me, self.n1)) if self.fz else e0)      # stage A's output: e0 itself for the dense Linear
+        bias = None if self.fz else self.o('encoder.input_linear.bias')
         if self.in_h2:
-            check(self.lib.mtl_gemm_h2_tb(self.st, 1, Me, d, d_in, p2.data_ptr(), d_in, self.am(SLOT['p2']), AMAX_STRIDE, wp.data_ptr(), d_in,
-                                          self.am(SLOT['wp']), s_am, e0.data_ptr(), d, self.o('encoder.input_linear.bias'), None, 0, nt, Me * d_in,
-                                          s_w, Me * d, self.sP, eng.gemm_ws.data_ptr(), eng.gemm_ws.numel() * 4), 'mtl_gemm_h2_tb')
+            check(self.lib.mtl_gemm_h2_tb(self.st, 1, Me, n1, d_in, p2.data_ptr(), d_in, self.am(SLOT['p2']), AMAX_STRIDE, wp.data_ptr(), d_in,
+                                          self.am(SLOT['wp']), s_am, ea.data_ptr(), n1, bias, None, 0, nt, Me * d_in,
+                                          s_w, Me * n1, self.sP, eng.gemm_ws.data_ptr(), eng.gemm_ws.numel() * 4), 'mtl_gemm_h2_tb')
         else:
-            eng.gemm(0, 1, Me, d, d_in, p2.data_ptr(), d_in, wp.data_ptr(), d_in, e0.data_ptr(), d, bias=self.o('encoder.input_linear.bias'),
-                     task=(Me * d_in, s_w, Me * d, self.sP, 0))
+            eng.gemm(0, 1, Me, n1, d_in, p2.data_ptr(), d_in, wp.data_ptr(), d_in, ea.data_ptr(), n1, bias=bias,
+                     task=(Me * d_in, s_w, Me * n1, self.sP, 0))
+        if self.fz:
+            eng.linear_fwd(ea.data_ptr(), Me, n1, self.o('encoder.input_linear_b.weight'), self.o('encoder.input_linear_b.bias'), e0.data_ptr(), d)
         return e0
 
     # ---- backward
     def linear_bwd(self, de0):
         """input_linear.weight += permuted (de0^T . p2); h2: the bound of de0 first (both products of the backward read it)"""
-        eng, st, nt, Me, d, d_in = self.eng, self.st, self.nt, self.Me, self.d, self.d_in
+        eng, st, nt, Me, d, d_in = self.eng, self.st, self.nt, self.Me, self.n1, self.d_in
         (T4, F4), p2, a8 = self.TF[2], self.A['p2'], self.am(SLOT['de0'])
+        if self.fz:     # stage B first: its weight gradient (the bias came from the input LayerNorm's dsum) and d(e0a), which stage A's two
+            dea = eng.buf('_de0a', (nt * Me, d))                    # products then take in de0's place (and in its bound slot); d = r below
+            eng.linear_bwd(self.A['e0a'].data_ptr(), de0.data_ptr(), Me, d, self.d, self.o('encoder.input_linear_b.weight'),
+                           self.g('encoder.input_linear_b.weight'), None, dea.data_ptr(), False)
+            eng.flush_side()
+            de0 = dea
+        self.de_in = de0
         dwp = eng.buf('_dwp', (nt, d, d_in))
         eng.buf('_dp2', (nt * self.B, T4, F4, self.c_out))
         if self.in_h2:
@@ -286,12 +302,14 @@ class Front:
                                              dwp.data_ptr(), d_in, nt, Me * d, Me * d_in, d * d_in), 'mtl_gemm_h2_tn_tb')
         else:
             eng.gemm(1, 0, d, d_in, Me, de0.data_ptr(), d, p2.data_ptr(), d_in, dwp.data_ptr(), d_in, task=(Me * d, Me * d_in, d * d_in, 0, 0))
-        check(self.lib.mtl_permute_hc_tb(st, dwp.data_ptr(), self.g('encoder.input_linear.weight'), d, self.c_out, F4, 1, None, nt, d * d_in, self.sG, 0),
+        check(self.lib.mtl_permute_hc_tb(st, dwp.data_ptr(), self.g(self.w_in), d, self.c_out, F4, 1, None, nt, d * d_in, self.sG, 0),
               'permute_inv')
 
     def linear_dgrad(self, de0):
-        """dp2 = (de0 . wp) gated by p2 > 0, straight from the un-transposed weight, all tasks in one launch"""
-        eng, nt, Me, d, d_in, (s_am, s_w) = self.eng, self.nt, self.Me, self.d, self.d_in, self.wp_strides
+        """dp2 = (de0 . wp) gated by p2 > 0, straight from the un-transposed weight, all tasks in one launch (factorized: d(e0a), which
+        linear_bwd formed, against the permuted input_linear_a)"""
+        eng, nt, Me, d, d_in, (s_am, s_w) = self.eng, self.nt, self.Me, self.n1, self.d_in, self.wp_strides
+        de0 = self.de_in
         p2, wp, dp2 = self.A['p2'], self.A['wp_in'], self.A['_dp2']
         if self.in_h2:
             check(self.lib.mtl_gemm_h2_tb(self.st, 0, Me, d_in, d, de0.data_ptr(), d, self.am(SLOT['de0']), AMAX_STRIDE, wp.data_ptr(), d_in,

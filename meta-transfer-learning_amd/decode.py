@@ -71,6 +71,18 @@ class _DecodeSession:
         else:
             self.kc = [buf('g.kc%d' % i, (B, S, hk)) for i in range(hp.n_dec)]
             self.vc = [buf('g.vc%d' % i, (B, S, hv)) for i in range(hp.n_dec)]
+        # --is-factorized: the feed-forward pairs are merged the same way, once per session (linear_1_b . linear_1_a -> (inner, d),
+        # linear_2_b . linear_2_a -> (d, inner)): a step runs the dense model's two calls per layer on them
+        self.ffn = []
+        for i in range(hp.n_dec):
+            o = lambda n, i=i: self.P + 4 * eng.L.off('decoder.layers.%d.pos_ffn.%s' % (i, n))
+            if eng.factorized:
+                w1, w2 = buf('g.wf1%d' % i, (hp.inner, d)), buf('g.wf2%d' % i, (d, hp.inner))
+                eng.gemm(0, 0, hp.inner, d, r, o('linear_1_b.weight'), r, o('linear_1_a.weight'), d, w1.data_ptr(), d)
+                eng.gemm(0, 0, d, hp.inner, r, o('linear_2_b.weight'), r, o('linear_2_a.weight'), hp.inner, w2.data_ptr(), hp.inner)
+                self.ffn.append((w1.data_ptr(), o('linear_1_b.bias'), w2.data_ptr(), o('linear_2_b.bias')))
+            else:
+                self.ffn.append((o('linear_1.weight'), o('linear_1.bias'), o('linear_2.weight'), o('linear_2.bias')))
         Bm = self.groups if shared_memory else B
         self.cross_stride = 0 if shared_memory else T4
         self.ck = [buf('g.ck%d' % i, (Bm * T4, hk)) for i in range(hp.n_dec)]
@@ -183,9 +195,9 @@ class _DecodeSession:
                 self._lowrank(ca, 'output', self.to.data_ptr(), B, self.tob.data_ptr(), width=d)
             eng.ln_fwd(self.tob.data_ptr(), self.y1.data_ptr(), o('encoder_attn.layer_norm.weight'), o('encoder_attn.layer_norm.bias'), None,
                        None, self.y2.data_ptr(), self.xhat.data_ptr(), self.rstd.data_ptr(), B, 1)
-            eng.linear_fwd(self.y2.data_ptr(), B, d, o('pos_ffn.linear_1.weight'), o('pos_ffn.linear_1.bias'), self.h1.data_ptr(), hp.inner,
-                           relu=True)
-            eng.linear_fwd(self.h1.data_ptr(), B, hp.inner, o('pos_ffn.linear_2.weight'), o('pos_ffn.linear_2.bias'), self.h2.data_ptr(), d)
+            w1, b1, w2, b2 = self.ffn[i]
+            eng.linear_fwd(self.y2.data_ptr(), B, d, w1, b1, self.h1.data_ptr(), hp.inner, relu=True)
+            eng.linear_fwd(self.h1.data_ptr(), B, hp.inner, w2, b2, self.h2.data_ptr(), d)
             nxt = self.cur[i & 1]                  # (the layer's output lands where the next layer reads it: no copy)
             eng.ln_fwd(self.h2.data_ptr(), self.y2.data_ptr(), o('pos_ffn.layer_norm.weight'), o('pos_ffn.layer_norm.bias'), None, None,
                        nxt.data_ptr(), self.xhat.data_ptr(), self.rstd.data_ptr(), B, 1)

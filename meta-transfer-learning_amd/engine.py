@@ -179,6 +179,15 @@ class PassEngine:
         # reads its parameters at theta + t * sP floats (0: all tasks share theta0 -- the training passes) and accumulates its
         # gradients at grad + t * sG (see forward_device / backward)
         self.nt, self.sP, self.sG = 1, 0, 0
+        # --is-factorized (model-wide: Hyper.factorized): the feed-forward Linears and the encoder's input Linear are rank-r pairs.
+        # ffn_mid_fused: the two inner products of the factorized block (r -> inner with bias + ReLU, inner -> r) as the one streamed
+        # kernel of csrc/mtl_ffn_lr.hip instead of two product calls; OFF by default -- see DESIGN.md section 20 for the measurement the
+        # default follows.  Shapes outside mtl_ffn_lr_mid_supported take the two calls either way.
+        # forward_only (set around passes that no backward follows: in-loop validation, Transformer.evaluate): the fused kernel then
+        # does not store the post-ReLU activation, and a backward() after such a pass raises
+        self.factorized = bool(getattr(hp, 'factorized', False))
+        self.ffn_mid_fused = False
+        self.forward_only = False
         self.prof = None    # set (to anything) while a profiling proxy stands in for self.lib: replay / graphs / lane tricks are bypassed
         # recorded call sequences of the searches (decode.py): greedy (one unit per decode), host-ranked beam (one per position),
         # device-ranked beam (one per block of BEAM_POLL positions); beam_pin: pinned read-back of the latter's done flags
@@ -789,14 +798,41 @@ class PassEngine:
             return [('q', xq, Mq), ('kv', xkv, Mk)]
         return [('q', xq, Mq), ('k', xkv, Mk), ('v', xkv, Mk)]
 
+    def _ffn_lr_fwd(self, tag, o, x, rows, h2):
+        """the factorized block's four Linears (modules/common_layers.py:134-158): x -> a1 (r) -> h1 (inner, bias + ReLU) -> c2 (r) ->
+        h2 (d, bias); the middle two as one launch with ffn_mid_fused.  tag + 'h1' stays the post-ReLU inner activation."""
+        hp, R = self.hp, self.nt * rows
+        r, inner = hp.r, hp.inner
+        a1 = self.buf(tag + 'a1', (R, r))
+        c2 = self.buf(tag + 'c2', (R, r))
+        self.linear_fwd(x, rows, hp.d, o('linear_1_a.weight'), None, a1.data_ptr(), r)
+        if self.ffn_mid_fused and self.lib.mtl_ffn_lr_mid_supported(r, inner):
+            if self.forward_only:
+                self.arena.pop(tag + 'h1', None)
+                h1p = None
+            else:
+                h1p = self.buf(tag + 'h1', (R, inner)).data_ptr()
+            check(self.lib.mtl_ffn_lr_mid_fwd(self.stream, a1.data_ptr(), r, o('linear_1_b.weight'), o('linear_1_b.bias'),
+                                              o('linear_2_a.weight'), h1p, c2.data_ptr(), r, rows, r, inner, self.nt, rows * r, self.sP,
+                                              rows * inner, rows * r), 'mtl_ffn_lr_mid_fwd')
+        else:
+            h1 = self.buf(tag + 'h1', (R, inner))
+            self.linear_fwd(a1.data_ptr(), rows, r, o('linear_1_b.weight'), o('linear_1_b.bias'), h1.data_ptr(), inner, relu=True)
+            self.linear_fwd(h1.data_ptr(), rows, inner, o('linear_2_a.weight'), None, c2.data_ptr(), r)
+        self.linear_fwd(c2.data_ptr(), rows, r, o('linear_2_b.weight'), o('linear_2_b.bias'), h2.data_ptr(), hp.d)
+
     def ffn_fwd(self, tag, P, pre, x, rows, T, keep):
         hp, L = self.hp, self.L
         o = lambda n: P + 4 * L.off(pre + n)
         R = self.nt * rows                             # rows: per task
-        h1 = self.buf(tag + 'h1', (R, hp.inner))
-        h2 = self.buf(tag + 'h2', (R, hp.d))
-        self.linear_fwd(x, rows, hp.d, o('linear_1.weight'), o('linear_1.bias'), h1.data_ptr(), hp.inner, relu=True)
-        self.linear_fwd(h1.data_ptr(), rows, hp.inner, o('linear_2.weight'), o('linear_2.bias'), h2.data_ptr(), hp.d)
+        if self.factorized:
+            h2 = self.buf(tag + 'h2', (R, hp.d))
+            self._ffn_lr_fwd(tag, o, x, rows, h2)
+        else:
+            h1 = self.buf(tag + 'h1', (R, hp.inner))
+            h2 = self.buf(tag + 'h2', (R, hp.d))
+            self.linear_fwd(x, rows, hp.d, o('linear_1.weight'), o('linear_1.bias'), h1.data_ptr(), hp.inner, relu=True)
+            self.linear_fwd(h1.data_ptr(), rows, hp.inner, o('linear_2.weight'), o('linear_2.bias'), h2.data_ptr(), hp.d)
         y = self.buf(tag + 'y', (R, hp.d))
         xhat = self.buf(tag + 'xhat', (R, hp.d))
         rstd = self.buf(tag + 'rstd', (R,))
@@ -814,12 +850,27 @@ class PassEngine:
         mf = A.get(tag + 'mf')
         dzm = self.buf(tag + '_dzm', (R, hp.d)) if mf is not None else None
         self.ln_bwd(dy, A[tag + 'xhat'].data_ptr(), A[tag + 'rstd'].data_ptr(), o('layer_norm.weight'), keep, dzb.data_ptr(),
-                    g('layer_norm.weight'), g('layer_norm.bias'), rows, dsum=g('linear_2.bias'), xmask=mf,
-                    dzm=dzm.data_ptr() if dzm is not None else None, dz2=dx)         # dx = dz: the residual path
+                    g('layer_norm.weight'), g('layer_norm.bias'), rows, dsum=g('linear_2_b.bias' if self.factorized else 'linear_2.bias'),
+                    xmask=mf, dzm=dzm.data_ptr() if dzm is not None else None, dz2=dx)         # dx = dz: the residual path
         dbr = dzm.data_ptr() if dzm is not None else dzb.data_ptr()
         h1 = A[tag + 'h1']
         dh1 = self.buf(tag + '_dh1', (R, hp.inner))
         kd = _LAYER_BUF.sub(r'\1*.\3', tag)
+        if self.factorized:
+            # four Linears, last to first; linear_2_b.bias came from the LayerNorm backward's dsum, linear_1_b.bias rides on its
+            # weight-gradient product; every weight gradient is logged under its kind, so the layers of a stack merge
+            r = hp.r
+            dc2, da1 = self.buf(tag + '_dc2', (R, r)), self.buf(tag + '_da1', (R, r))
+            self.linear_bwd(A[tag + 'c2'].data_ptr(), dbr, rows, r, hp.d, o('linear_2_b.weight'), g('linear_2_b.weight'), None,
+                            dc2.data_ptr(), False, kind=kd + 'w2b')
+            self.linear_bwd(h1.data_ptr(), dc2.data_ptr(), rows, hp.inner, r, o('linear_2_a.weight'), g('linear_2_a.weight'), None,
+                            dh1.data_ptr(), False, gate=h1.data_ptr(), kind=kd + 'w2a')
+            self.linear_bwd(A[tag + 'a1'].data_ptr(), dh1.data_ptr(), rows, r, hp.inner, o('linear_1_b.weight'), g('linear_1_b.weight'),
+                            g('linear_1_b.bias'), da1.data_ptr(), False, kind=kd + 'w1b')
+            self.linear_bwd(x, da1.data_ptr(), rows, hp.d, r, o('linear_1_a.weight'), g('linear_1_a.weight'), None, dx, True,
+                            kind=kd + 'w1a')
+            self.flush_side()
+            return
         self.linear_bwd(h1.data_ptr(), dbr, rows, hp.inner, hp.d, o('linear_2.weight'), g('linear_2.weight'),
                         None, dh1.data_ptr(), False, gate=h1.data_ptr(), kind=kd + 'w2')
         self.linear_bwd(x, dh1.data_ptr(), rows, hp.d, hp.inner, o('linear_1.weight'), g('linear_1.weight'),
@@ -1052,7 +1103,8 @@ class PassEngine:
             check(lib.mtl_ctc_fwd(st, pred.data_ptr(), gold_ptr, meta['ctc_in_len'], meta['ctc_tgt_len'], Bt, Td, V, V, Td,
                                   Lmax, PAD_ID, B, ctc['ws'].data_ptr(), ws_bytes, ctc['nll'].data_ptr(), loss.data_ptr()), 'ctc_fwd')
         self.saved = dict(S, Td=Td, n_nonpad=n_nonpad, smoothing=float(smoothing), klen_enc=klen_enc, klen_dec=klen_dec, keep_enc=keep_enc,
-                          keep_dec=keep_dec, dec_last=cur, enc_inputs=enc_inputs, loss_type=loss_type, ctc=ctc)
+                          keep_dec=keep_dec, dec_last=cur, enc_inputs=enc_inputs, loss_type=loss_type, ctc=ctc,
+                          no_backward=bool(self.factorized and self.forward_only))
         if self.forward_hook is not None:
             self.forward_hook(self)
         # T4 / frames: the extent of the arena's encoder-side activations (a widened stand-alone pass, PassEngine.forward, carries
@@ -1091,6 +1143,8 @@ class PassEngine:
         S = self.saved
         if S is None:
             raise RuntimeError('backward() without a preceding forward()')
+        if S.get('no_backward'):
+            raise RuntimeError('backward() after a forward_only pass: its activations were not kept')
         hp, L, lib, st, A = self.hp, self.L, self.lib, self.stream, self.arena
         nt = S['nt']
         if dmem_hook is not None and nt > 1:
@@ -1203,7 +1257,7 @@ class PassEngine:
         de0 = dnext
         self.ln_bwd(dcur.data_ptr(), A['enc_in.xhat'].data_ptr(), A['enc_in.rstd'].data_ptr(), o('encoder.layer_norm_input.weight'),
                     None, de0.data_ptr(), g('encoder.layer_norm_input.weight'), g('encoder.layer_norm_input.bias'), Me,
-                    dsum=g('encoder.input_linear.bias'))
+                    dsum=g('encoder.input_linear_b.bias' if self.factorized else 'encoder.input_linear.bias'))
         self.flush_layer_wgrads()       # the encoder stack's weight gradients
         # input Linear and VGG front-end (convstack.py), in the mode the forward recorded
         front = convstack.Front(self, S, G, sG)

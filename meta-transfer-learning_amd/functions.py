@@ -37,7 +37,7 @@ def init_transformer_model(args, vocab, train=True, is_factorized=False, r=100):
                       dim_model=args.dim_model, dim_inner=args.dim_inner, dim_key=args.dim_key, dim_value=args.dim_value,
                       trg_max_length=args.tgt_max_len, dropout=args.dropout, emb_trg_sharing=args.emb_trg_sharing,
                       is_factorized=is_factorized, r=r)
-    return Transformer(encoder, decoder, vocab, feat_extractor=args.feat_extractor, train=train)
+    return Transformer(encoder, decoder, vocab, feat_extractor=args.feat_extractor, train=train, is_factorized=is_factorized, r=r)
 
 
 def post_process(string, special_token_list):
@@ -56,6 +56,12 @@ def _as_torch_opt(opt):
     return opt.to_torch() if hasattr(opt, 'to_torch') else opt
 
 
+def _record_model_switches(args, model):
+    """args.is_factorized / args.r as the model was built: the loaders of both stacks rebuild from them (utils/functions.py:172-175); a
+    model built through init_transformer_model(..., is_factorized=True) from arguments that do not say so still reloads as it is"""
+    args.is_factorized, args.r = bool(model.is_factorized), int(model.r)
+
+
 def save_meta_model(model, vocab, epoch, inner_opt, outer_opt, metrics, args, best_model=False):
     """utils/functions.py:101-126: the same `.th` dict ('vocab', 'args', 'epoch', 'model_state_dict', 'inner_opt', 'outer_opt',
     'metrics').  Written so that BOTH stacks can read it: tensors on the CPU; the optimizers as real
@@ -67,6 +73,7 @@ def save_meta_model(model, vocab, epoch, inner_opt, outer_opt, metrics, args, be
     os.makedirs(folder, exist_ok=True)
     print('SAVE MODEL to', save_path)
     logging.info('SAVE MODEL to ' + save_path)
+    _record_model_switches(args, model)
     state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     params = [torch.nn.Parameter(state[n], requires_grad=True) for n, _ in model.named_parameters()]
     payload = {'vocab': vocab, 'args': args, 'epoch': epoch, 'model_state_dict': state,
@@ -83,6 +90,7 @@ def save_joint_model(model, vocab, epoch, opt, metrics, args, best_model=False):
     os.makedirs(folder, exist_ok=True)
     print('SAVE MODEL to', save_path)
     logging.info('SAVE MODEL to ' + save_path)
+    _record_model_switches(args, model)
     state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     params = [torch.nn.Parameter(state[n], requires_grad=True) for n, _ in model.named_parameters()]
     payload = {'vocab': vocab, 'args': args, 'epoch': epoch, 'model_state_dict': state, 'opt': _export_opt(opt, params),

@@ -9,7 +9,8 @@ through the engine's `greedy_decode` / `beam_decode` / `beam_decode_batch` (the 
 
 Reference symbols mirrored: Transformer (models/asr/transformer.py:14-240), Encoder/EncoderLayer
 (modules/encoder.py:15-106), Decoder/DecoderLayer (modules/decoder.py:14-115,293-323),
-FactorizedMultiHeadAttention / PositionwiseFeedForward / PositionalEncoding (modules/common_layers.py:86-132,238-306).
+FactorizedMultiHeadAttention / PositionwiseFeedForward / FactorizedPositionwiseFeedForward / PositionalEncoding
+(modules/common_layers.py:86-158,238-306).
 """
 import math
 import os
@@ -65,53 +66,74 @@ class PositionwiseFeedForward(nn.Module):
         self.layer_norm = nn.LayerNorm(dim_model)
 
 
+class FactorizedPositionwiseFeedForward(nn.Module):
+    """--is-factorized: both Linears as rank-r pairs (modules/common_layers.py:134-158); the `_a` halves carry no bias."""
+
+    def __init__(self, dim_model, dim_ff, dropout=0.1, r=100):
+        super().__init__()
+        self.linear_1_a = nn.Linear(dim_model, r, bias=False)
+        self.linear_1_b = nn.Linear(r, dim_ff)
+        self.linear_2_a = nn.Linear(dim_ff, r, bias=False)
+        self.linear_2_b = nn.Linear(r, dim_model)
+        self.layer_norm = nn.LayerNorm(dim_model)
+
+
+def _pos_ffn(dim_model, dim_inner, dropout, is_factorized, r):
+    if is_factorized:
+        return FactorizedPositionwiseFeedForward(dim_model, dim_inner, dropout=dropout, r=r)
+    return PositionwiseFeedForward(dim_model, dim_inner, dropout=dropout)
+
+
 class EncoderLayer(nn.Module):
     def __init__(self, num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=0.1, is_factorized=False, r=100):
         super().__init__()
+        self.is_factorized, self.r = is_factorized, r
         self.self_attn = FactorizedMultiHeadAttention(num_heads, dim_model, dim_key, dim_value, dropout=dropout, r=r)
-        self.pos_ffn = PositionwiseFeedForward(dim_model, dim_inner, dropout=dropout)
+        self.pos_ffn = _pos_ffn(dim_model, dim_inner, dropout, is_factorized, r)
 
 
 class Encoder(nn.Module):
     def __init__(self, num_layers, num_heads, dim_model, dim_key, dim_value, dim_input, dim_inner, dropout=0.1,
                  src_max_length=2500, is_factorized=False, r=100):
         super().__init__()
-        if is_factorized:
-            raise NotImplementedError('--is-factorized (factorized FFN / input projection) is outside the accelerated path')
         self.num_layers, self.num_heads, self.dim_model = num_layers, num_heads, dim_model
         self.dim_key, self.dim_value, self.dim_input, self.dim_inner = dim_key, dim_value, dim_input, dim_inner
-        self.src_max_length, self.dropout_rate, self.r = src_max_length, dropout, r
-        self.input_linear = nn.Linear(dim_input, dim_model)
+        self.src_max_length, self.dropout_rate, self.is_factorized, self.r = src_max_length, dropout, is_factorized, r
+        if is_factorized:                                   # modules/encoder.py:40-44
+            self.input_linear_a = nn.Linear(dim_input, r, bias=False)
+            self.input_linear_b = nn.Linear(r, dim_model)
+        else:
+            self.input_linear = nn.Linear(dim_input, dim_model)
         self.layer_norm_input = nn.LayerNorm(dim_model)
         self.positional_encoding = PositionalEncoding(dim_model, src_max_length)
-        self.layers = nn.ModuleList([EncoderLayer(num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=dropout, r=r)
-                                     for _ in range(num_layers)])
+        self.layers = nn.ModuleList([EncoderLayer(num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=dropout,
+                                                  is_factorized=is_factorized, r=r) for _ in range(num_layers)])
 
 
 class DecoderLayer(nn.Module):
     def __init__(self, dim_model, dim_inner, num_heads, dim_key, dim_value, dropout=0.1, is_factorized=False, r=100):
         super().__init__()
+        self.is_factorized, self.r = is_factorized, r
         self.self_attn = FactorizedMultiHeadAttention(num_heads, dim_model, dim_key, dim_value, dropout=dropout, r=r)
         self.encoder_attn = FactorizedMultiHeadAttention(num_heads, dim_model, dim_key, dim_value, dropout=dropout, r=r)
-        self.pos_ffn = PositionwiseFeedForward(dim_model, dim_inner, dropout=dropout)
+        self.pos_ffn = _pos_ffn(dim_model, dim_inner, dropout, is_factorized, r)
 
 
 class Decoder(nn.Module):
     def __init__(self, vocab, num_layers, num_heads, dim_emb, dim_model, dim_inner, dim_key, dim_value, dropout=0.1,
                  trg_max_length=1000, emb_trg_sharing=False, is_factorized=False, r=100):
         super().__init__()
-        if is_factorized or emb_trg_sharing:
-            raise NotImplementedError('factorized FFN / shared target embedding are outside the accelerated path')
         if dim_emb != dim_model:
             raise ValueError('dim_emb must equal dim_model (the reference adds the embedding to a dim_model table)')
         self.vocab = vocab
         self.num_layers, self.num_heads, self.dim_emb, self.dim_model = num_layers, num_heads, dim_emb, dim_model
         self.dim_inner, self.dim_key, self.dim_value = dim_inner, dim_key, dim_value
-        self.trg_max_length, self.dropout_rate, self.r = trg_max_length, dropout, r
+        self.trg_max_length, self.dropout_rate, self.is_factorized, self.r = trg_max_length, dropout, is_factorized, r
+        self.emb_trg_sharing = emb_trg_sharing              # stored and never read, as in modules/decoder.py:32
         self.trg_embedding = nn.Embedding(len(vocab.label2id), dim_emb, padding_idx=vocab.PAD_ID)
         self.positional_encoding = PositionalEncoding(dim_model, max_length=trg_max_length)
-        self.layers = nn.ModuleList([DecoderLayer(dim_model, dim_inner, num_heads, dim_key, dim_value, dropout=dropout, r=r)
-                                     for _ in range(num_layers)])
+        self.layers = nn.ModuleList([DecoderLayer(dim_model, dim_inner, num_heads, dim_key, dim_value, dropout=dropout,
+                                                  is_factorized=is_factorized, r=r) for _ in range(num_layers)])
         self.output_linear = nn.Linear(dim_model, len(vocab.label2id), bias=False)
         nn.init.xavier_normal_(self.output_linear.weight)
 
@@ -170,7 +192,10 @@ class Transformer(nn.Module):
         if feat_extractor not in ('vgg_cnn', 'large_cnn'):
             raise NotImplementedError("only feat_extractor='vgg_cnn' and 'large_cnn' are on the accelerated path")
         self.encoder, self.decoder, self.vocab = encoder, decoder, vocab
-        self.feat_extractor, self.is_factorized, self.r = feat_extractor, is_factorized, r
+        if bool(encoder.is_factorized) != bool(decoder.is_factorized):
+            raise ValueError('encoder and decoder are built with one --is-factorized value in the reference factory')
+        # (the reference's factory leaves the Transformer's own is_factorized / r at their defaults: the blocks' are what counts)
+        self.feat_extractor, self.is_factorized, self.r = feat_extractor, bool(encoder.is_factorized), encoder.r
         self.copy_grad = None
         if encoder.dropout_rate != decoder.dropout_rate:
             raise ValueError('encoder and decoder are built with one --dropout value in the reference factory')
@@ -216,7 +241,8 @@ class Transformer(nn.Module):
             e, d = self.encoder, self.decoder
             hp = Hyper(d=e.dim_model, r=e.r, h=e.num_heads, dk=e.dim_key, dv=e.dim_value, inner=e.dim_inner,
                        d_in=e.dim_input, n_enc=e.num_layers, n_dec=d.num_layers, V=len(self.vocab.label2id),
-                       temperature=np.power(e.dim_key, 0.5), src_max_len=e.src_max_length, tgt_max_len=d.trg_max_length)
+                       temperature=np.power(e.dim_key, 0.5), src_max_len=e.src_max_length, tgt_max_len=d.trg_max_length,
+                       factorized=self.is_factorized)
             pe_e, pe_d = e.positional_encoding.pe[0].contiguous(), d.positional_encoding.pe[0].contiguous()
             # task lanes: independent tasks of a meta-step run concurrently, each on its own stream with its own arena
             self.engines = [PassEngine(self._layout, hp, device, pe_e, pe_d) for _ in range(self.n_lanes)]
@@ -365,10 +391,11 @@ class Transformer(nn.Module):
         ids_nbest = None
         try:
             widen, eng.widen = eng.widen, '0'          # the decoders read the encoder output in the batch's own extent (T4 positions per utterance)
+            eng.forward_only = True                    # no backward follows (a factorized model's fused feed-forward keeps no activation)
             try:
                 out = self.pass_forward(padded_input, input_lengths, padded_target)
             finally:
-                eng.widen = widen
+                eng.widen, eng.forward_only = widen, False
             B, T = padded_input.shape[0], padded_input.shape[3]
             T4 = (T // 2) // 2
             mem = eng.arena['e%d.ff.y' % (eng.hp.n_enc - 1)] if eng.hp.n_enc else eng.arena['enc_in.y']

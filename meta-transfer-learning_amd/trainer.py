@@ -203,7 +203,10 @@ def run_validation(forward_one_batch, model, vocab, valid_loader_list, it, args,
     dev = model.flat_parameters.device
     model.eval()
     final_losses, final_cers = [], []
+    engines = getattr(model, 'engines', [])
     try:
+        for e in engines:
+            e.forward_only = True                   # PassEngine.forward_only: no backward follows these passes
         with torch.no_grad():
             for ind, loader in enumerate(valid_loader_list):
                 tot_loss, tot_cer, tot_char, nb = 0.0, 0, 0, 0
@@ -222,6 +225,8 @@ def run_validation(forward_one_batch, model, vocab, valid_loader_list, it, args,
                 say(msg)
                 logging.info(msg)
     finally:
+        for e in engines:
+            e.forward_only = False
         model.train()
     if not final_losses:
         return False, best, count_stop
