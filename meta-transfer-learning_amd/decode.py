@@ -10,6 +10,7 @@ import math
 import numpy as np
 import torch
 
+from . import passplan
 from ._lib import check
 from .batchmeta import EOS_ID, PAD_ID
 
@@ -40,7 +41,7 @@ class _DecodeSession:
         # strided-batch launches writing row t, and the attention over the cache is ONE flash-attention launch (keys beyond the current
         # position masked by a per-step length: row t of `klen_self`) instead of product + softmax + product
         self.fast = bool(eng.fused_attn and hk == hv and hp.n_dec > 0 and
-                         eng._qkv_groups('decoder.layers.0.self_attn.', 1, 1, 1, 1, hk, hv)[0][0] == 'qkv')
+                         passplan.qkv_groups(eng.L, 'decoder.layers.0.self_attn.', 1, 1, 1, 1, hk, hv)[0][0] == 'qkv')
         if self.fast:
             self.qkv = [buf('g.qkv%d' % i, (3, B, S, hk)) for i in range(hp.n_dec)]
             for c in self.qkv:
@@ -61,7 +62,7 @@ class _DecodeSession:
             for i in range(hp.n_dec):
                 pre = 'decoder.layers.%d.' % i
                 o = lambda n, pre=pre: self.P + 4 * eng.L.off(pre + n)
-                sA_, sB_ = (eng._pstride(pre + 'self_attn.', 'qkv', sfx) for sfx in ('_linear_a.weight', '_linear_b.weight'))
+                sA_, sB_ = (passplan.pstride(eng.L, pre + 'self_attn.', 'qkv', sfx) for sfx in ('_linear_a.weight', '_linear_b.weight'))
                 eng.gemm(0, 0, hk, d, r, o('self_attn.query_linear_b.weight'), r, o('self_attn.query_linear_a.weight'), d, self.Wqkv[i].data_ptr(), d,
                          batch=3, sA=(sB_, 0), sB=(sA_, 0), sC=(hk * d, 0))
                 for att, dst in (('self_attn.', self.Wso[i]), ('encoder_attn.', self.Wco[i])):
@@ -154,7 +155,7 @@ class _DecodeSession:
             o = lambda n: P + 4 * L.off(pre + n)
             sa = pre + 'self_attn.'
             if self.fast:
-                sb_ = eng._pstride(sa, 'qkv', '_linear_b.bias')
+                sb_ = passplan.pstride(L, sa, 'qkv', '_linear_b.bias')
                 qkv = self.qkv[i].data_ptr()
                 eng.gemm(0, 1, B, hk, d, cur.data_ptr(), d, self.Wqkv[i].data_ptr(), d, qkv + 4 * t * hk, S * hk,
                          bias=o('self_attn.query_linear_b.bias'), batch=3, sB=(hk * d, 0), sC=(B * S * hk, 0), sbias=sb_)

@@ -11,20 +11,19 @@ What a pass computes follows the reference line by line:
   models/asr/transformer.py:120-149 (forward), modules/encoder.py:53-106, modules/decoder.py:71-115,293-323,
   modules/common_layers.py:110-132,238-331, utils/metrics.py:96-126.
 """
+import functools
 import os
 
 import numpy as np
 import torch
 
-import re
-
-from . import _lib, _trace, convstack, decode
+from . import _lib, _trace, convstack, decode, passplan
 from ._lib import check
 from .batchmeta import PAD_ID, SOS_ID, EOS_ID, batch_meta, decoder_io, ctc_input_lengths      # noqa: F401  (callers import the ids and the two helpers from here)
 from .convstack import CENSUS_NAMES, CENSUS_SLOTS      # noqa: F401  (the bound slots of the h2 operands; the trainer's h2 guard names them)
 from .decode import beam_unpack                         # noqa: F401
-
-RELU, ACCUM = 1, 2
+from .passplan import ACCUM, RELU, FULL as _FULL, round_width      # noqa: F401  (metastep.py imports round_width from here)
+from .pool import BufferPool, LAYER_BUF as _LAYER_BUF
 
 
 class ParamLayout:
@@ -72,66 +71,20 @@ class Hyper:
 
 
 LOSS_TYPES = ('ce', 'ctc')
-_FULL = {'q': 'query', 'k': 'key', 'v': 'value'}
-
 STAGE_RING = 6      # pinned staging buffers per slot (prepare_tasks): > pipeline depth (default 2) + 2
 
-_LAYER_BUF = re.compile(r'^([de])(\d+)\.(.+)$')
 
-
-def round_width(T, quantum):
-    """Frame count rounded up to a repeating width: a multiple of `quantum`, coarser for long batches (at most 1/16 of the width, so the
-    padding stays below ~6 % while a 5000-frame workload -- 55 GB of buffers per width -- sees a handful of widths, not dozens)."""
-    q = max(int(quantum), 1)
-    q = max(q, (T // 16) // q * q)
-    return -(-T // q) * q
-
-
-_POOL_ACCOUNTS = {}
-
-
-def _pool_account(device):
-    """Bytes held by the buffer pools of every engine on one device, and the budget they share (MTL_POOL_GB)."""
-    key = (device.type, device.index)
-    acc = _POOL_ACCOUNTS.get(key)
-    if acc is None:
-        gb = os.environ.get('MTL_POOL_GB')
-        if gb is not None:
-            budget = int(float(gb) * (1 << 30))
-        elif device.type == 'cuda':
-            budget = max(torch.cuda.get_device_properties(device).total_memory // 4, 4 << 30)
-        else:
-            budget = 4 << 30
-        acc = _POOL_ACCOUNTS[key] = dict(bytes=0, budget=budget, gen=0, engines=[])
-    return acc
-
-
-class PassEngine:
+class PassEngine(BufferPool):
     def __init__(self, layout, hp, device, pe_enc, pe_dec):
+        super().__init__(device, {'d': hp.n_dec, 'e': hp.n_enc})     # arena, pool, the device's shared budget, scratch_epoch: pool.py
         self.pe_enc, self.pe_dec = pe_enc, pe_dec   # (max_len, d) fp32 device tables (non-trainable buffers)
         self.L = layout
         self.hp = hp
-        self.device = device
         self.lib = _lib.lib()
-        self.arena = {}     # name -> buffer of the current pass (looked up again by the backward)
-        self.pool = {}      # (name, shape, dtype) -> allocation, so alternating batch shapes do not re-allocate
-        # Real manifests bring a new (T, Td) with almost every batch (collate pads to the batch maximum; padding further would change
-        # results: the reference masks with RAW frame counts, SURVEY Q2).  The pool is therefore bounded: entries carry the number
-        # of the last pass that touched them, and trim_pool() -- start of every forward -- drops the least recently used ones that
-        # neither this pass nor the previous one uses while the pools of ALL engines on this device (a model has one per task lane)
-        # together hold more than MTL_POOL_GB (default: a quarter of the device's memory, 72 GiB of the 288; a budget per engine let
-        # eight lanes keep 8 x 48 GiB of stale shapes and ran a north-star run on ragged batches out of memory).  An eviction bumps
-        # scratch_epoch, which makes the trainer re-record its command lists (they hold raw addresses).
-        self.account = _pool_account(device)
-        import weakref
-        self.account['engines'] = [w for w in self.account['engines'] if w() is not None] + [weakref.ref(self)]
-        self._last_pass = self.account['gen']       # the device-wide pass count at this engine's latest pass (trim_pool)
         # stand-alone passes on batches whose width changes from call to call are widened to repeating widths ('auto': from the second
         # width on; '0' never -- Transformer.evaluate; '1' always), to a multiple of MTL_RAGGED_QUANTUM frames
         self.widen, self.widen_quantum = 'auto', int(os.environ.get('MTL_RAGGED_QUANTUM', '64'))
         self._first_width, self._widths_vary = {}, False
-        self.pool_budget = self.account['budget']           # (an engine may be given a tighter one of its own: tests)
-        self._pool_gen, self._pool_bytes, self._gen = {}, 0, 0
         self.saved = None
         self.gemm_ws = torch.empty(8 << 20, dtype=torch.float32, device=device) if device.type == 'cuda' else None  # split-K slabs
         # weight/bias-gradient kernels are off the critical path (nothing downstream in the backward reads them): they run
@@ -140,7 +93,6 @@ class PassEngine:
         self.gemm_ws_side = torch.empty(8 << 20, dtype=torch.float32, device=device) if device.type == 'cuda' else None
         self.scratch_side = torch.empty(4 << 20, dtype=torch.float32, device=device) if device.type == 'cuda' else None
         self.on_side = False
-        self.scratch_epoch = 0
         self._stage, self._stage_turn = {}, {}   # pinned host staging of prepare()
         self._events, self._ev_next = [], 0    # fork / join events of the side stream (raw handles: recordable library calls)
         self.dropout_p = 0.0          # set by the model: hp.dropout when model.training else 0
@@ -197,103 +149,17 @@ class PassEngine:
             raise RuntimeError('PassEngine needs an MI355X device (got %s); there is no CPU product path' % device)
 
     # ---------------------------------------------------------------- plumbing
-    def _took(self, nbytes):
-        self._pool_bytes += nbytes
-        self.account['bytes'] += nbytes
-
-    def __del__(self):
-        try:
-            self.account['bytes'] -= self._pool_bytes     # the device-wide account outlives the engine
-        except Exception:
-            pass
-
-    def buf(self, name, shape, dtype=torch.float32):
-        """Named buffer of the current pass.  Per-layer buffers ('d<i>.<what>', 'e<i>.<what>') are slices of ONE allocation per
-        <what> with the layers at a constant stride -- 'dec_in.y' / 'enc_in.y' are slot 0 of the '<x>.ff.y' group, so that every
-        layer's INPUT is at that stride too -- which lets the weight-gradient products of all layers of a stack run as one
-        strided-batch launch (flush_layer_wgrads)."""
-        shape = tuple(int(v) for v in shape)
-        m = _LAYER_BUF.match(name)
-        if m or name in ('dec_in.y', 'enc_in.y'):
-            kind, idx, rest = (m.group(1), int(m.group(2)), m.group(3)) if m else (name[0], -1, 'ff.y')
-            n = (self.hp.n_dec if kind == 'd' else self.hp.n_enc) + (1 if rest == 'ff.y' else 0)
-            slot = idx + 1 if rest == 'ff.y' else idx
-            if 0 <= slot < n:
-                key = (kind + '*.' + rest, (n,) + shape, dtype)
-                grp = self.pool.get(key)
-                if grp is None:
-                    grp = torch.empty(key[1], dtype=dtype, device=self.device)
-                    self.pool[key] = grp
-                    self._took(grp.numel() * grp.element_size())
-                self._pool_gen[key] = self._gen
-                t = grp[slot]
-                self.arena[name] = t
-                return t
-        key = (name, shape, dtype)
-        t = self.pool.get(key)
-        if t is None:
-            t = torch.empty(key[1], dtype=dtype, device=self.device)
-            self.pool[key] = t
-            self._took(t.numel() * t.element_size())
-        self._pool_gen[key] = self._gen
-        self.arena[name] = t
-        return t
-
-    def _evict(self, evictable):
-        """drop the least recently used pool entries `evictable(key)` accepts while the pool / the device-wide account is over its
-        budget; -> bytes freed.  An eviction invalidates everything that holds addresses (tables, arena, recorded command lists)."""
-        over = lambda: self._pool_bytes > self.pool_budget or self.account['bytes'] > self.account['budget']
-        freed = 0
-        for key in sorted(self.pool, key=lambda k: self._pool_gen.get(k, 0)):
-            if not over() or not evictable(key):
-                break
-            t = self.pool.pop(key)
-            self._pool_gen.pop(key, None)
-            nb = t.numel() * t.element_size()
-            self._took(-nb)
-            freed += nb
-        if freed:
-            # device tables keyed by buffer addresses (LayerNorm reductions) and the pinned staging of shapes that are gone: rebuilt on
-            # demand
-            self._ln_tables.clear()
-            self.arena = {k: v for k, v in self.arena.items() if not isinstance(v, torch.Tensor) or k == '_scratch'}
-            self.scratch_epoch += 1
-        return freed
+    def _pool_invalidated(self):
+        self._ln_tables.clear()     # device tables keyed by buffer addresses (LayerNorm reductions): rebuilt on demand
 
     def trim_pool(self):
-        """Start of a pass: count it, and while the pool is over its budget drop least-recently-used buffers that the last two
-        passes did not touch (a forward and its backward, and the pass a pipelined host has already enqueued, keep theirs).
-        The budget is shared by all engines of the device (a model has one per task lane), and an engine can only give up its OWN
-        buffers during its own pass: when the shared account is over, the engines that have been IDLE for a while (no pass among the
-        device's last max(8, 4 x engines) passes: lanes a changed schedule no longer uses) are emptied first -- otherwise the one
-        engine doing the work would stay over budget for ever, dropping and re-allocating its own shapes (and re-recording the
-        trainer's command lists) on every pass.
-        Frees go back to torch's caching allocator in stream order: the side stream was joined at the end of the backward, and a
-        block returns to the free list of the stream it was allocated on."""
-        self._gen += 1
-        acc = self.account
-        acc['gen'] += 1
-        self._last_pass = acc['gen']
+        """BufferPool.trim_pool (start of a pass: count it, evict while over budget), and the bound on the engine's own tables"""
+        freed = super().trim_pool()
         if len(self._ln_tables) > 512:
             # descriptor tables are keyed by addresses AND extents: ragged batches bring new ones with every pass.  Recorded command
             # lists hold the tables' addresses, hence the epoch.
             self._ln_tables.clear()
             self.scratch_epoch += 1
-        over = lambda: self._pool_bytes > self.pool_budget or acc['bytes'] > acc['budget']
-        if not over():
-            return 0
-        if torch.cuda.is_current_stream_capturing():
-            return 0                      # a free inside a hipGraph capture would be baked into the graph: trim at the next eager pass
-        freed = 0
-        if acc['bytes'] > acc['budget']:
-            others = [e for e in (w() for w in acc['engines']) if e is not None and e is not self]
-            idle_after = max(8, 4 * (len(others) + 1))
-            for e in sorted(others, key=lambda e_: e_._last_pass):
-                if acc['bytes'] <= acc['budget'] or acc['gen'] - e._last_pass < idle_after:
-                    break
-                freed += e._evict(lambda key: True)
-        if over():
-            freed += self._evict(lambda key: self._pool_gen.get(key, 0) < self._gen - 2)
         return freed
 
     def scratch(self, nbytes):
@@ -301,12 +167,7 @@ class PassEngine:
             if nbytes > self.scratch_side.numel() * 4:
                 raise RuntimeError('side-stream scratch too small for %d bytes' % nbytes)
             return self.scratch_side.data_ptr()
-        t = self.arena.get('_scratch')
-        if t is None or t.numel() * 4 < nbytes:
-            t = torch.empty((int(nbytes) + 3) // 4 + 1024, dtype=torch.float32, device=self.device)
-            self.arena['_scratch'] = t
-            self.scratch_epoch += 1          # recorded command lists hold the old address: their keys start over (_lib.Replay)
-        return t.data_ptr()
+        return super().scratch(nbytes)
 
     @property
     def stream(self):
@@ -376,30 +237,11 @@ class PassEngine:
             (int(C), int(A), int(B), int(rowsum or 0)))
 
     def flush_layer_wgrads(self):
-        """Issue the logged weight-gradient products on the side stream.  The entries of a kind differ only in their four pointers;
-        when those advance by constant strides from layer to layer (they do: per-layer buffers and the parameters of a stack sit at
-        constant strides) the whole kind is ONE launch with the layer as outer batch index -- 4 x the workgroups of a single layer's
-        product (64 tiles: a quarter of the chip), a quarter of the launches and no fork per sub-layer block."""
+        """Issue the logged weight-gradient products on the side stream: one strided-batch launch per kind where the layers'
+        pointers advance by constant strides (passplan.merge_wgrad_jobs)."""
         log, self._wlog = self._wlog, {}
-        for (kind, M, N, K, lda, ldb, ldc, n, sA, sB, sC, srow, has_rs), items in log.items():
-            items.sort()
-            nl = len(items)
-            steps = [tuple(b[j] - a[j] for j in range(4)) for a, b in zip(items, items[1:])]
-            merged = nl > 1 and all(st == steps[0] for st in steps) and all(v % 16 == 0 for v in steps[0])
-            tk = (K * lda, K * ldb, self.sG, 0, self.sG)       # task t: its K rows of dy / x, its slice of the gradient stack
-            if merged:
-                dC, dA, dB, dR = (v // 4 for v in steps[0])
-                C0, A0, B0, R0 = items[0]
-                self.defer(lambda M=M, N=N, K=K, A0=A0, lda=lda, B0=B0, ldb=ldb, C0=C0, ldc=ldc, nl=nl, n=n, dA=dA, sA=sA, dB=dB, sB=sB,
-                           dC=dC, sC=sC, R0=R0, dR=dR, srow=srow, has_rs=has_rs, tk=tk: self.gemm(
-                    1, 0, M, N, K, A0, lda, B0, ldb, C0, ldc, flags=ACCUM, batch=nl * n, H=n, sA=(dA, sA), sB=(dB, sB), sC=(dC, sC),
-                    rowsum=R0 if has_rs else None, srow=dR, srow_h=srow, task=tk))
-            else:
-                for C0, A0, B0, R0 in items:
-                    self.defer(lambda M=M, N=N, K=K, A0=A0, lda=lda, B0=B0, ldb=ldb, C0=C0, ldc=ldc, n=n, sA=sA, sB=sB, sC=sC, R0=R0,
-                               srow=srow, has_rs=has_rs, tk=tk: self.gemm(
-                        1, 0, M, N, K, A0, lda, B0, ldb, C0, ldc, flags=ACCUM, batch=n, sA=(sA, 0), sB=(sB, 0), sC=(sC, 0),
-                        rowsum=R0 if has_rs else None, srow=srow, task=tk))
+        for a, kw in passplan.merge_wgrad_jobs(log, self.sG):
+            self.defer(functools.partial(self.gemm, *a, **kw))
         self.flush_side()
 
     # ---- side stream: deferred parameter-gradient work
@@ -560,7 +402,7 @@ class PassEngine:
         # The three projections have identical shapes and their parameters sit at a constant stride in the flat theta / G
         # buffers, so projections that share their input run as ONE strided-batch GEMM per low-rank stage (self-attention:
         # q,k,v; encoder-decoder attention: k,v) instead of two launches (+ a split-K reduction) each.
-        groups = self._qkv_groups(pre, xq, Mq, xkv, Mk, hk, hv)
+        groups = passplan.qkv_groups(L, pre, xq, Mq, xkv, Mk, hk, hv)
         for names, src, rows in groups:
             n, f0 = len(names), _FULL[names[0]]
             wd = hv if names == 'v' else hk                  # groups of several projections exist only when hk == hv
@@ -574,7 +416,7 @@ class PassEngine:
             R = nt * rows
             a_all = self.buf(tag + names + 'a', (n, R, r))
             b_all = self.buf(tag + names, (n, R, wd))
-            sa, sb, sbias = (self._pstride(pre, names, sfx) for sfx in ('_linear_a.weight', '_linear_b.weight', '_linear_b.bias'))
+            sa, sb, sbias = (passplan.pstride(L, pre, names, sfx) for sfx in ('_linear_a.weight', '_linear_b.weight', '_linear_b.bias'))
             self.gemm(0, 1, rows, r, d, src, d, o(f0 + '_linear_a.weight'), d, a_all.data_ptr(), r, batch=n, sB=(sa, 0),
                       sC=(R * r, 0), task=(rows * d, sP, rows * r, 0, 0))
             self.gemm(0, 1, rows, wd, r, a_all.data_ptr(), r, o(f0 + '_linear_b.weight'), r, b_all.data_ptr(), wd,
@@ -690,7 +532,7 @@ class PassEngine:
             a_all, d_all = A[tag + names + 'a'], dfull[names]
             R = nt * rows
             da_all = self.buf(tag + '_da' + names, (n, R, r))
-            sa, sb, sbias = (self._pstride(pre, names, sfx) for sfx in ('_linear_a.weight', '_linear_b.weight', '_linear_b.bias'))
+            sa, sb, sbias = (passplan.pstride(L, pre, names, sfx) for sfx in ('_linear_a.weight', '_linear_b.weight', '_linear_b.bias'))
             a_ptr, d_ptr, da_ptr = a_all.data_ptr(), d_all.data_ptr(), da_all.data_ptr()
 
             # dW_b[i] += d[i]^T a[i]  and  db_b[i] += colsum(d[i])
@@ -713,28 +555,9 @@ class PassEngine:
         self.flush_side()
 
     # ---- encoder-decoder attention: K / V projections of all decoder layers in one go
-    def _cross_kv_plan(self, Mk):
-        """(layer stride, projection stride) in floats when the K / V low-rank parameters of the decoder layers' encoder_attn blocks
-        sit at constant strides in the flat buffer (they do for the reference's module tree), else None."""
-        hp, L = self.hp, self.L
-        if hp.n_dec < 2 or hp.dk != hp.dv:
-            return None
-        plan = None
-        for sfx in ('_linear_a.weight', '_linear_b.weight', '_linear_b.bias'):
-            k = [L.off('decoder.layers.%d.encoder_attn.key%s' % (i, sfx)) for i in range(hp.n_dec)]
-            v = [L.off('decoder.layers.%d.encoder_attn.value%s' % (i, sfx)) for i in range(hp.n_dec)]
-            ls = {b - a for a, b in zip(k, k[1:])}
-            ps = {b - a for a, b in zip(k, v)}
-            if len(ls) != 1 or len(ps) != 1 or min(ls) <= 0 or min(ps) <= 0 or (min(ls) | min(ps)) % 4:
-                return None
-            if plan is not None and plan != (min(ls), min(ps)):
-                return None
-            plan = (min(ls), min(ps))
-        return plan
-
     def cross_kv_fwd(self, P, mem, Mk):
         """k_l, v_l = W_b (W_a mem) (+ b) for every decoder layer l: two launches with batch = 2 n_dec (layers outer, k / v inner)."""
-        plan = self._cross_kv_plan(Mk)
+        plan = passplan.cross_kv_plan(self.L, self.hp.n_dec, self.hp.dk, self.hp.dv)
         self.arena['xkv.plan'] = plan
         if plan is None:
             return None
@@ -775,28 +598,6 @@ class PassEngine:
             self.gemm(0, 0, Mk, d, r, da_ptr + 4 * pj * Rk * r, r, o0(name + '_linear_a.weight'), d, dmem, d, flags=ACCUM if pj else 0,
                       kbatch=NL, sAk=2 * Rk * r, sBk=Ls, task=(Mk * r, sP, Mk * d, 0, 0))
         self.flush_side()
-
-    def _pstride(self, pre, names, suffix):
-        """Distance (floats) between consecutive projections' parameters `suffix` in the flat buffer (0 for a single one)."""
-        if len(names) == 1:
-            return 0
-        offs = [self.L.off(pre + _FULL[nm] + suffix) for nm in names]
-        return offs[1] - offs[0]
-
-    def _qkv_groups(self, pre, xq, Mq, xkv, Mk, hk, hv):
-        """[(names, input pointer, rows)]: projections that can share one strided-batch launch."""
-        def uniform(names):
-            for sfx in ('_linear_a.weight', '_linear_b.weight', '_linear_b.bias'):
-                offs = [self.L.off(pre + _FULL[nm] + sfx) for nm in names]
-                steps = {b - a for a, b in zip(offs, offs[1:])}
-                if len(steps) != 1 or min(steps) <= 0 or min(steps) % 4:
-                    return False
-            return hk == hv
-        if xq == xkv and Mq == Mk and uniform('qkv'):
-            return [('qkv', xq, Mq)]
-        if uniform('kv'):
-            return [('q', xq, Mq), ('kv', xkv, Mk)]
-        return [('q', xq, Mq), ('k', xkv, Mk), ('v', xkv, Mk)]
 
     def _ffn_lr_fwd(self, tag, o, x, rows, h2):
         """the factorized block's four Linears (modules/common_layers.py:134-158): x -> a1 (r) -> h1 (inner, bias + ReLU) -> c2 (r) ->

@@ -177,11 +177,12 @@ def _model(name, perturb=None):
 
 
 def _off_the_fused_path(name, model):
+    from mtl_amd import passplan
     eng = model.engine
     assert not eng.fused_attn
-    groups = [g[0] for g in eng._qkv_groups('decoder.layers.0.self_attn.', 1, 1, 1, 1, eng.hp.h * eng.hp.dk, eng.hp.h * eng.hp.dv)]
+    groups = [g[0] for g in passplan.qkv_groups(eng.L, 'decoder.layers.0.self_attn.', 1, 1, 1, 1, eng.hp.h * eng.hp.dk, eng.hp.h * eng.hp.dv)]
     assert groups == (['qkv'] if name == 'A' else ['q', 'k', 'v'])
-    assert (eng._cross_kv_plan(1) is not None) == (name == 'A')
+    assert (passplan.cross_kv_plan(eng.L, eng.hp.n_dec, eng.hp.dk, eng.hp.dv) is not None) == (name == 'A')
 
 
 def _oracle(name, perturb=None):
