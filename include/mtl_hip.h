@@ -352,6 +352,24 @@ int mtl_ffn_lr_mid_supported(int r, int inner);
 int mtl_ffn_lr_mid_fwd(void* stream, const float* a, int lda, const float* B1, const float* b1, const float* A2, float* h, float* c,
                        int ldc, int rows, int r, int inner, int tasks, long sAt, long sWt, long sHt, long sCt);
 
+/* ---- the encoder's input Linear of a model without a convolutional front-end (feat_extractor 'none'; csrc/mtl_featproj.hip) on the
+ * feature planes as the batch brings them and the weight as nn.Linear stores it:
+ *   y[(b T + p), n] = bias[n] + sum_f x[b, f, p] w[n, f]        for every sample b < B and frame p < T of every task
+ * x (B, F, T) fp32 planes, w (N, F) row-major, bias (N; nullable), y (B T, N) dense.  Task t < tasks reads x + t * sX (0: all tasks
+ * share one batch), w and bias + t * sW (0: all tasks share the parameters; the two stand in one parameter buffer), writes
+ * y + t * sY (floats).  Any F, T, N >= 1; NO alignment is asked of any operand or row, and nothing is read past an operand's end.
+ * Exact bf16 triples, six MFMAs per block product, fixed order: bitwise reproducible, and a task's result does not depend on `tasks`.
+ * MTL_EINVAL before any launch for null operands (bias excepted), non-positive extents, negative strides, B or tasks > 65535. */
+int mtl_featproj_fwd_tb(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int F, int T, int N,
+                        int tasks, long sX, long sW, long sY);
+/* its weight gradient  dw_t[n, f] += sum_{b, p} dy_t[(b T + p), n] x_t[b, f, p]  (dy dense (B T, N), task stride sDy; dw at task stride
+ * sG floats, >= N F when tasks > 1).  The B T rows are split over the grid into `workspace` (mtl_featproj_wgrad_workspace bytes; the
+ * split depends on B T, F and N alone, never on `tasks`) and summed in a fixed order: no atomics, bitwise reproducible, per task bitwise the one-task launch.
+ * MTL_EINVAL as above, and for a null or too small workspace. */
+long mtl_featproj_wgrad_workspace(int B, int F, int T, int N, int tasks);
+int mtl_featproj_wgrad_tb(void* stream, const float* x, const float* dy, float* dw, float* workspace, long workspace_bytes, int B,
+                          int F, int T, int N, int tasks, long sX, long sDy, long sG);
+
 /* ---- embedding + positional encoding: modules/decoder.py:96 ------------------------------------------- */
 int mtl_embed_pe_fwd(void* stream, const long* ids, const float* table, const float* pe, float* out, int rows, int T, int d,
                      const unsigned char* mask /*nullable: dropout keep-mask*/, float mscale);

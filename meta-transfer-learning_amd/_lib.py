@@ -96,6 +96,9 @@ SIGNATURES = {
     'mtl_attn_bwd': (I, [P, P, P, P, I, I, I, P, I, F, I, I, I, I, I, I, P, I, F, P, P, I, P, P, P, P, P, I, I, I]),
     'mtl_ffn_lr_mid_supported': (I, [I, I]),
     'mtl_ffn_lr_mid_fwd': (I, [P, P, I, P, P, P, P, P, I, I, I, I, I, L, L, L, L]),
+    'mtl_featproj_fwd_tb': (I, [P, P, P, P, P, I, I, I, I, I, L, L, L]),
+    'mtl_featproj_wgrad_workspace': (L, [I, I, I, I, I]),
+    'mtl_featproj_wgrad_tb': (I, [P, P, P, P, P, L, I, I, I, I, I, L, L, L]),
     'mtl_embed_pe_fwd': (I, [P, P, P, P, P, I, I, I, P, F]),
     'mtl_embed_bwd': (I, [P, P, P, P, P, P, I, I, L, P, F]),
     'mtl_embed_pe_fwd_g': (I, [P, P, P, P, P, I, I, I, P, F, I, L]),

@@ -5,6 +5,14 @@ import numpy as np
 import torch
 
 PAD_ID, SOS_ID, EOS_ID = 0, 1, 2
+CONV_TIME_SHIFT = 2         # the conv stacks' two 2 x 2 max-pools: T frames -> (T // 2) // 2 encoder positions
+
+
+def enc_extent(frames, time_shift=CONV_TIME_SHIFT):
+    """THE definition of the encoder's extent: positions the encoder holds for `frames` input frames (an int or an integer array).
+    time_shift: log2 of the front-end's time reduction -- 2 behind the conv stacks ((T // 2) // 2 = T >> 2), 0 for a model without a
+    feature extractor, whose frames ARE the positions (PassEngine.time_shift derives it from the parameter layout)."""
+    return frames >> time_shift
 
 
 def decoder_io(padded_target, pad_id=PAD_ID, sos_id=SOS_ID, eos_id=EOS_ID, width=None):
@@ -50,19 +58,21 @@ def _occurrence_chains(flat_in, base):
     return first, nxt
 
 
-def batch_meta(batches, B, T, src_max_len, tgt_max_len, norm_count=None, width=None, frames=None, percentages=None, target_sizes=None):
+def batch_meta(batches, B, T, src_max_len, tgt_max_len, norm_count=None, width=None, frames=None, percentages=None, target_sizes=None,
+               time_shift=CONV_TIME_SHIFT):
     """The host side of PassEngine.prepare_tasks (which documents the arguments) for the batches [(lengths, target)] of the tasks of one
-    pass; src_max_len / tgt_max_len: rows of the positional tables.  -> dict with
+    pass; src_max_len / tgt_max_len: rows of the positional tables; time_shift: the model's, see enc_extent (0: every frame is an encoder
+    position, so klen_enc / keep_enc mask the batch's real padding).  -> dict with
       meta: the int32 block, fields in the order of `off`; its two seed words are left 0 for the caller to fill
       off: {field: word offset inside meta} for seed, inv_count, klen_enc, klen_dec, keep_enc, keep_dec, embed_first, embed_next,
            widths (None without per-task frames), ctc_in_len, ctc_tgt_len
       seq_in, seq_out: (nt * B, Td) int64 decoder input / gold ids, tasks concatenated
       Td, frames (normalised: None when every task fills T), n_nonpads, gold_hosts, ctc_in_len_host, ctc_tgt_len_host: per task."""
     nt = len(batches)
-    T4 = (T // 2) // 2
+    T4 = enc_extent(T, time_shift)
     if frames is not None:
         frames = [int(f) for f in frames]
-        if len(frames) != nt or max(frames) > T or min(frames) < 4:
+        if len(frames) != nt or max(frames) > T or enc_extent(min(frames), time_shift) < 1:
             raise ValueError('frames: one count per task, none above the padded width')
         if all(f == T for f in frames):
             frames = None
@@ -94,7 +104,7 @@ def batch_meta(batches, B, T, src_max_len, tgt_max_len, norm_count=None, width=N
         ctc_in.append(ctc_input_lengths(pct, int(n_lab.max()) + 1))
         ctc_tg.append(sizes.astype(np.int32))
         if frames is not None:
-            lens = np.minimum(lens, (frames[ti] // 2) // 2)     # a position the task's own pass does not have is padding
+            lens = np.minimum(lens, enc_extent(frames[ti], time_shift))     # a position the task's own pass does not have is padding
         is_pad = seq_in == EOS_ID
         dec_len = (~is_pad).sum(1)
         if not bool((is_pad == (dpos >= dec_len[:, None])).all()):

@@ -7,6 +7,8 @@ adapter per precision mode (which call, which argument order), one walker per di
     layer's tails being cleared for all tasks before the next layer reads them;
   * 'x3' and 'h2' issue ONE `_tb` launch per layer for the samples of all tasks when the pass carries several tasks or `widths` (a
     single widened task takes the several-task launches too: they skip its tail rows), else the single-task call for the one task.
+A model without convolutions (feat_extractor='none') takes FrameFront instead, the same five methods around csrc/mtl_featproj.hip
+(front_for chooses; time_shift tells the two kinds' encoder extents apart).
 PassEngine._forward_device / .backward call in here through a Front, which uses the engine's buf / scratch / colsum / gemm / _census.
 A Front takes eng.lib when it is made, once per direction, as the pass itself does: bench.py and the command-list recorder swap that
 attribute around whole passes.  One kept across such a swap would go on calling the library it was made with, past the recorder."""
@@ -16,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .batchmeta import CONV_TIME_SHIFT
 
 # the bounds max|tensor| of the h2 operands (csrc/mtl_h2.h): AMAX_PER_TASK slots of _lib.AMAX_SLOTS floats per task, raised by the
 # producers' epilogues (forward), written by the bias-gradient column sums or delivered by the data-gradient epilogues (backward)
@@ -48,7 +51,10 @@ STACKS = {'vgg_cnn': LAYERS, 'large_cnn': LAYERS_LARGE}
 
 
 def layers_for(layout):
-    """the layer table of a model, by the output channels of its conv0 (ParamLayout)"""
+    """the layer table of a model, by the output channels of its conv0 (ParamLayout); None: the model has no convolutions
+    (feat_extractor='none': the features go straight into the encoder, FrameFront)"""
+    if 'conv.0.weight' not in layout.entries:
+        return None
     c0 = layout.entries['conv.0.weight'][1][0]
     for layers in STACKS.values():
         if layers[0].cin == c0:
@@ -59,7 +65,8 @@ def layers_for(layout):
 def decide(eng, nt, widths):
     """what the front-end of a pass runs on, read ONCE at the start of its forward from the engine's assignable attributes, kept in `saved`.
     A large_cnn model runs on the exact split whatever conv_h2 / conv_x3 say: its 32-channel layers exist in that arithmetic only
-    (csrc/mtl_conv_narrow.hip), so conv_mode is 'x3', in_h2 is False and the trainer's periodic h2 census is skipped."""
+    (csrc/mtl_conv_narrow.hip), so conv_mode is 'x3', in_h2 is False and the trainer's periodic h2 census is skipped.  The same holds for a
+    model without convolutions (conv_layers None): its input Linear exists on the exact split only (csrc/mtl_featproj.hip)."""
     mode = 'h2' if eng.conv_h2 else ('x3' if eng.conv_x3 else 'f32')
     if eng.conv_layers is not LAYERS:
         mode = 'x3'
@@ -350,3 +357,70 @@ class Front:
             else:
                 check((lib.mtl_conv0c_wgrad if c0 else lib.mtl_conv0_wgrad)(*head), 'wgrad0')
         self.census(('_dp2', '_dy5', '_dp1'))
+
+
+class FrameFront:
+    """The front of a model WITHOUT convolutions (feat_extractor='none', models/asr/transformer.py:93-94: the (B, 1, F, T) batch viewed as
+    (B, F, T) and transposed; modules/encoder.py: Linear(F -> d) on every frame), with Front's five methods.  There is nothing to
+    convolve and no data gradient (the features carry none); the input Linear and its weight gradient run on the feature planes as the
+    batch brings them and the weight as theta holds it (csrc/mtl_featproj.hip: no transposed or padded copy of either), all tasks of
+    the pass in one launch.  Every frame is an encoder position: tasks stacked at the widest bring zero frames beyond their own width
+    (the batch builder pads with zeros), whose rows come out as the bias and are masked like any padding (batchmeta: klen_enc, keep_enc).
+    --is-factorized: stage A (input_linear_a, r x F, no bias) is the same kernel at N = r; stage B and its backward are Front's."""
+
+    def __init__(self, eng, S, G=None, sG=0):
+        self.eng, self.lib, self.st, self.A = eng, eng.lib, eng.stream, eng.arena
+        self.nt, self.sP, self.sX, self.B, self.x, self.sG = S['nt'], S['sP'], S['sX'], S['B'], S['x'], sG
+        self.T, self.F = S['T'], S['F']
+        self.d, self.Me = eng.hp.d, self.B * self.T                             # (Me: encoder rows per task)
+        self.fz = eng.factorized
+        self.n1 = eng.hp.r if self.fz else self.d
+        self.w_in = 'encoder.input_linear_a.weight' if self.fz else 'encoder.input_linear.weight'
+        P, sP, off = S['theta'].data_ptr(), self.sP, eng.L.off
+        self.o = lambda n: P + 4 * off(n)                                       # (the stack's base: the launches stride the tasks)
+        self.g = lambda n: G + 4 * off(n)
+
+    def convs_fwd(self):
+        pass
+
+    def linear_fwd(self):
+        """e0 = x^T . w^T + b for every frame of every task"""
+        eng, nt, Me, d, n1 = self.eng, self.nt, self.Me, self.d, self.n1
+        e0 = eng.buf('e0', (nt * Me, d))
+        ea = eng.buf('e0a', (nt * Me, n1)) if self.fz else e0
+        bias = None if self.fz else self.o('encoder.input_linear.bias')
+        check(self.lib.mtl_featproj_fwd_tb(self.st, self.x.data_ptr(), self.o(self.w_in), bias, ea.data_ptr(), self.B, self.F, self.T, n1, nt,
+                                           self.sX, self.sP, Me * n1), 'mtl_featproj_fwd_tb')
+        if self.fz:
+            eng.linear_fwd(ea.data_ptr(), Me, n1, self.o('encoder.input_linear_b.weight'), self.o('encoder.input_linear_b.bias'), e0.data_ptr(), d)
+        return e0
+
+    def linear_bwd(self, de0):
+        """input_linear.weight += de0^T . x^T (the bias came from the input LayerNorm's dsum); factorized: stage B's weight gradient and
+        d(e0a) first, as in Front.linear_bwd"""
+        eng, nt, Me, n1 = self.eng, self.nt, self.Me, self.n1
+        if self.fz:
+            dea = eng.buf('_de0a', (nt * Me, n1))
+            eng.linear_bwd(self.A['e0a'].data_ptr(), de0.data_ptr(), Me, n1, self.d, self.o('encoder.input_linear_b.weight'),
+                           self.g('encoder.input_linear_b.weight'), None, dea.data_ptr(), False)
+            eng.flush_side()
+            de0 = dea
+        need = self.lib.mtl_featproj_wgrad_workspace(self.B, self.F, self.T, n1, nt)
+        check(self.lib.mtl_featproj_wgrad_tb(self.st, self.x.data_ptr(), de0.data_ptr(), self.g(self.w_in), eng.scratch(need), need, self.B,
+                                             self.F, self.T, n1, nt, self.sX, Me * n1, self.sG), 'mtl_featproj_wgrad_tb')
+
+    def linear_dgrad(self, de0):
+        pass
+
+    def convs_bwd(self):
+        pass
+
+
+def front_for(eng, S, G=None, sG=0):
+    """the front of a pass in one direction: the conv stack's (Front) or, for a model without convolutions, FrameFront"""
+    return (FrameFront if eng.conv_layers is None else Front)(eng, S, G, sG)
+
+
+def time_shift(layout):
+    """log2 of the front-end's time reduction (batchmeta.enc_extent): two max-pools behind either conv stack, none without one"""
+    return CONV_TIME_SHIFT if 'conv.0.weight' in layout.entries else 0

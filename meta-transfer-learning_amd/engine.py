@@ -19,7 +19,7 @@ import torch
 
 from . import _lib, _trace, convstack, decode, passplan
 from ._lib import check
-from .batchmeta import PAD_ID, SOS_ID, EOS_ID, batch_meta, decoder_io, ctc_input_lengths      # noqa: F401  (callers import the ids and the two helpers from here)
+from .batchmeta import PAD_ID, SOS_ID, EOS_ID, batch_meta, decoder_io, ctc_input_lengths, enc_extent      # noqa: F401  (callers import the ids and the two helpers from here)
 from .convstack import CENSUS_NAMES, CENSUS_SLOTS      # noqa: F401  (the bound slots of the h2 operands; the trainer's h2 guard names them)
 from .decode import beam_unpack                         # noqa: F401
 from .passplan import ACCUM, RELU, FULL as _FULL, round_width      # noqa: F401  (metastep.py imports round_width from here)
@@ -119,7 +119,8 @@ class PassEngine(BufferPool):
             raise ValueError('MTL_CONV must be h2, x3 or f32')
         self.conv_x3 = self.conv_mode != 'f32'
         self.conv_h2 = self.conv_mode == 'h2'
-        self.conv_layers = convstack.layers_for(layout)     # vgg_cnn or large_cnn (the latter: always 'x3', convstack.decide)
+        self.conv_layers = convstack.layers_for(layout)     # vgg_cnn or large_cnn (the latter: always 'x3', convstack.decide); None: no convolutions
+        self.time_shift = convstack.time_shift(layout)      # T frames -> enc_extent(T) encoder positions: T >> 2 behind a conv stack, T without one
         self._ln_pending, self._ln_tables = [], {}
         # the encoder's input Linear (5120 -> 512) with its data / weight gradient: 'h2' with the h2 convolutions (two fp16 pieces, the
         # bounds ride along), else the product engines' own routing (x3 / fp32); bench.py's exact-fp32 leg sets 'f32'
@@ -161,6 +162,10 @@ class PassEngine(BufferPool):
             self._ln_tables.clear()
             self.scratch_epoch += 1
         return freed
+
+    def enc_extent(self, frames):
+        """encoder positions of a batch `frames` wide (batchmeta.enc_extent at this model's time reduction)"""
+        return enc_extent(int(frames), self.time_shift)
 
     def scratch(self, nbytes):
         if self.on_side:
@@ -702,7 +707,8 @@ class PassEngine(BufferPool):
         percentages = lengths / max(lengths) as data.py forms them, target_sizes = the count of non-PAD targets.  The two int32
         arrays (nt * B each) stand at the END of the meta block."""
         hp = self.hp
-        bm = batch_meta(batches, B, T, hp.src_max_len, hp.tgt_max_len, norm_count, width, frames, percentages, target_sizes)
+        bm = batch_meta(batches, B, T, hp.src_max_len, hp.tgt_max_len, norm_count, width, frames, percentages, target_sizes,
+                        time_shift=self.time_shift)
         meta_np, off, Td, nt = bm['meta'], bm['off'], bm['Td'], len(batches)
         # dropout seed of this pass (torch CPU RNG): drawn once the batch has been accepted
         meta_np[off['seed']:off['seed'] + 2] = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).numpy().view(np.int32)
@@ -762,7 +768,7 @@ class PassEngine(BufferPool):
         if self.widen == 'auto' and not self._widths_vary:
             self._widths_vary = self._first_width.setdefault(slot, T_own) != T_own
         if self.widen_quantum > 1 and (self.widen == '1' or (self.widen == 'auto' and self._widths_vary and self.forward_hook is None)):
-            Tq = max(min(round_width(T_own, self.widen_quantum), 4 * self.hp.src_max_len), T_own)
+            Tq = max(min(round_width(T_own, self.widen_quantum), self.hp.src_max_len << self.time_shift), T_own)
             if Tq != T_own:
                 xp = self.buf('fwd.x.%d' % slot, tuple(x.shape[:3]) + (Tq,))
                 xp.zero_()
@@ -798,7 +804,7 @@ class PassEngine(BufferPool):
         if Bx not in (B, nt * B) or T != meta['T']:
             raise ValueError('input batch does not match the prepared batch')
         sX = B * F * T if Bx == nt * B and nt > 1 else 0          # task stride of the input (0: one batch shared by all tasks)
-        if F // 2 // 2 * self.conv_layers[-1].cout != hp.d_in:
+        if (F if self.conv_layers is None else F // 2 // 2 * self.conv_layers[-1].cout) != hp.d_in:
             raise ValueError('dim_input %d does not match %d frequency bins' % (hp.d_in, F))
         if loss_type not in LOSS_TYPES:
             raise NotImplementedError("loss_type must be 'ce' or 'ctc'")
@@ -814,7 +820,7 @@ class PassEngine(BufferPool):
         hp, L, lib, st = self.hp, self.L, self.lib, self.stream
         sP = self.sP
         B = meta['B']
-        T4 = (T // 2) // 2
+        T4 = self.enc_extent(T)
         P = theta.data_ptr()
         o = lambda n: P + 4 * L.off(n)
         d, V = hp.d, hp.V
@@ -827,7 +833,7 @@ class PassEngine(BufferPool):
         # ---- VGG front-end (convstack.py) ----
         # what this pass runs on is decided here, once: the backward goes by this record, not by the engine's attributes of its time
         S = dict(theta=theta, x=x, B=B, T=T, F=F, meta=meta, nt=nt, sP=sP, sX=sX, **convstack.decide(self, nt, meta.get('widths')))
-        front = convstack.Front(self, S)
+        front = convstack.front_for(self, S)
         front.convs_fwd()
 
         # ---- encoder ----
@@ -932,7 +938,7 @@ class PassEngine(BufferPool):
             raise ValueError('encoder_output() is defined for single-task passes')
         hp = self.hp
         mem = self.arena['e%d.ff.y' % (hp.n_enc - 1)] if hp.n_enc else self.arena['enc_in.y']
-        return mem.view(S['B'], (S['T'] // 2) // 2, hp.d)
+        return mem.view(S['B'], self.enc_extent(S['T']), hp.d)
 
     def backward(self, grad, scale=1.0, dpred=None, sG=0, dmem_hook=None):
         """Accumulate `scale` * dLoss/dtheta of the LAST forward into the flat buffer `grad` (+=).
@@ -960,7 +966,7 @@ class PassEngine(BufferPool):
         o = lambda n: P + 4 * L.off(n)
         g = lambda n: G + 4 * L.off(n)
         B, T, Td = S['B'], S['T'], S['Td']
-        T4 = (T // 2) // 2
+        T4 = self.enc_extent(T)
         Me, Md, d, V = B * T4, B * Td, hp.d, hp.V                   # rows PER TASK
         keep_enc, keep_dec = S['keep_enc'], S['keep_dec']
 
@@ -1061,7 +1067,7 @@ class PassEngine(BufferPool):
                     dsum=g('encoder.input_linear_b.bias' if self.factorized else 'encoder.input_linear.bias'))
         self.flush_layer_wgrads()       # the encoder stack's weight gradients
         # input Linear and VGG front-end (convstack.py), in the mode the forward recorded
-        front = convstack.Front(self, S, G, sG)
+        front = convstack.front_for(self, S, G, sG)
         front.linear_bwd(de0)
         if self.slice_hook is not None:
             self.flush_ln_reduce()         # the encoder's LayerNorms (+ the input LayerNorm): their partials were all produced on this stream
@@ -1072,5 +1078,6 @@ class PassEngine(BufferPool):
         self.join_side()
         self.flush_ln_reduce()     # the parameter / bias gradients of all 17 LayerNorms of the pass: one launch (after the join: one of
                                    # the 17 backward kernels ran on the side stream)
-        self._slice_done('conv')
+        if self.conv_layers is not None:       # (a model without convolutions has no third parameter group to hand over)
+            self._slice_done('conv')
         self.nt, self.sP, self.sG = 1, 0, 0

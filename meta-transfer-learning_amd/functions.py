@@ -20,16 +20,20 @@ def init_transformer_model(args, vocab, train=True, is_factorized=False, r=100):
     of args.dim_input from the sample rate / window (161 bins -> 40 pooled rows x 128 channels = 5120), or 2560 for
     feat='logfbank' (LogFBankFrontEnd / LogFBankDataset: 80 bands -> 20 pooled rows).  feat_extractor='large_cnn' (:324-327): the
     same stack at half the width, 40 pooled rows x 64 channels = 2560."""
-    if args.feat_extractor not in ('vgg_cnn', 'large_cnn'):
-        raise NotImplementedError("only feat_extractor='vgg_cnn' and 'large_cnn' are on the accelerated path")
+    if args.feat_extractor not in ('vgg_cnn', 'large_cnn', 'none'):
+        raise NotImplementedError("only feat_extractor='vgg_cnn', 'large_cnn' and 'none' are on the accelerated path")
     logfbank = getattr(args, 'feat', 'spectrogram') == 'logfbank'
     if args.feat_extractor == 'large_cnn' and logfbank:
         raise NotImplementedError("feat_extractor='large_cnn' with feat='logfbank': the reference derives dim_input = 2560 from 161 "
                                   "spectrogram bins there, which 80 filterbank bands (20 pooled rows x 64 channels = 1280) cannot feed")
-    bins = int(math.floor((args.sample_rate * args.window_size) / 2) + 1)
-    args.dim_input = int(math.floor(int(math.floor(bins) / 2) / 2)) * (128 if args.feat_extractor == 'vgg_cnn' else 64)
-    if logfbank:
-        args.dim_input = 2560                                        # :322-323: 80 bands pool to 20 rows of 128 channels
+    if args.feat_extractor == 'none':
+        # :328-329: args.dim_input stays the caller's (161 spectrogram bins, 80 filterbank bands): the features go straight into the encoder
+        print('the model is initialized without feature extractor')
+    else:
+        bins = int(math.floor((args.sample_rate * args.window_size) / 2) + 1)
+        args.dim_input = int(math.floor(int(math.floor(bins) / 2) / 2)) * (128 if args.feat_extractor == 'vgg_cnn' else 64)
+        if logfbank:
+            args.dim_input = 2560                                    # :322-323: 80 bands pool to 20 rows of 128 channels
     encoder = Encoder(args.num_enc_layers, num_heads=args.num_heads, dim_model=args.dim_model, dim_key=args.dim_key,
                       dim_value=args.dim_value, dim_input=args.dim_input, dim_inner=args.dim_inner,
                       src_max_length=args.src_max_len, dropout=args.dropout, is_factorized=is_factorized, r=r)

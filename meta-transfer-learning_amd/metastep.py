@@ -13,6 +13,7 @@ import torch
 
 from . import _lib, _trace, convstack, dist as mdist
 from . import trainer as _trainer     # (imports this module in turn: clip_flat_grad_, cer_counts are looked up at call time)
+from .batchmeta import CONV_TIME_SHIFT, enc_extent
 from .engine import CENSUS_NAMES, CENSUS_SLOTS, PAD_ID, round_width
 
 check = _lib.check
@@ -56,7 +57,7 @@ def _label_width(targets, quantum, most):
 def _padded_width(eng, T, q):
     """T frames rounded up to a width that repeats (round_width, quantum q; q <= 1: T itself): any width at or above the batch's own
     is exact, up to what the positional table allows for the encoder length"""
-    return max(min(round_width(T, q), 4 * eng.hp.src_max_len), T) if q > 1 else T
+    return max(min(round_width(T, q), eng.hp.src_max_len << getattr(eng, 'time_shift', CONV_TIME_SHIFT)), T) if q > 1 else T
 
 
 def _padded_labels(tr, eng, targets, q):
@@ -334,7 +335,8 @@ def _can_batch(tr, model, task_batches, val_batch):
     if any(tuple(tb[0].shape[:3]) != shape[:3] for tb in task_batches):
         return False
     frames = [int(tb[0].shape[3]) for tb in task_batches]
-    return min(frames) >= 4 and sum(frames) >= tr.ragged_fill * len(frames) * max(frames)
+    # (every task needs at least one encoder position: 4 frames behind a conv stack, 1 without one)
+    return enc_extent(min(frames), getattr(eng, 'time_shift', CONV_TIME_SHIFT)) >= 1 and sum(frames) >= tr.ragged_fill * len(frames) * max(frames)
 
 
 def _batched_iteration(tr, step, task_batches, val_batch):
@@ -482,7 +484,7 @@ def _chunk_hook(tr, model, eng, accumulate_slice):
     if tr._comm_stream is None:
         tr._comm_stream = torch.cuda.Stream(dev)
     bounds = eng.slice_bounds()
-    if sorted(bounds) != ['conv', 'decoder', 'encoder']:
+    if sorted(set(bounds) | {'conv'}) != ['conv', 'decoder', 'encoder']:      # (a model without convolutions has the other two only)
         raise RuntimeError('unexpected parameter groups %s' % sorted(bounds))
     tr._chunks = mdist.ChunkedAllReduce()
     G, comm = model._G, tr._comm_stream

@@ -189,8 +189,8 @@ class _ModelEncFn(torch.autograd.Function):
 class Transformer(nn.Module):
     def __init__(self, encoder, decoder, vocab, feat_extractor='vgg_cnn', train=True, is_factorized=False, r=100):
         super().__init__()
-        if feat_extractor not in ('vgg_cnn', 'large_cnn'):
-            raise NotImplementedError("only feat_extractor='vgg_cnn' and 'large_cnn' are on the accelerated path")
+        if feat_extractor not in ('vgg_cnn', 'large_cnn', 'none'):
+            raise NotImplementedError("only feat_extractor='vgg_cnn', 'large_cnn' and 'none' are on the accelerated path")
         self.encoder, self.decoder, self.vocab = encoder, decoder, vocab
         if bool(encoder.is_factorized) != bool(decoder.is_factorized):
             raise ValueError('encoder and decoder are built with one --is-factorized value in the reference factory')
@@ -202,11 +202,14 @@ class Transformer(nn.Module):
         print('feat extractor:', feat_extractor)
         # indices 0,2,5,7 hold the convolutions exactly like the reference nn.Sequential (ReLU/MaxPool are parameter-free);
         # large_cnn (models/asr/transformer.py:60-72): the same stack at half the width
-        c1, c2 = (64, 128) if feat_extractor == 'vgg_cnn' else (32, 64)
-        self.conv = nn.Sequential(nn.Conv2d(1, c1, 3, stride=1, padding=1), nn.ReLU(),
-                                  nn.Conv2d(c1, c1, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2),
-                                  nn.Conv2d(c1, c2, 3, stride=1, padding=1), nn.ReLU(),
-                                  nn.Conv2d(c2, c2, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2))
+        # 'none' (models/asr/transformer.py:88-94): no `conv` attribute at all -- the parameters are the encoder's and the decoder's, no
+        # RNG draw between the Decoder's constructor and the xavier sweep; the (B, 1, F, T) batch feeds the input Linear frame by frame
+        if feat_extractor != 'none':
+            c1, c2 = (64, 128) if feat_extractor == 'vgg_cnn' else (32, 64)
+            self.conv = nn.Sequential(nn.Conv2d(1, c1, 3, stride=1, padding=1), nn.ReLU(),
+                                      nn.Conv2d(c1, c1, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2),
+                                      nn.Conv2d(c1, c2, 3, stride=1, padding=1), nn.ReLU(),
+                                      nn.Conv2d(c2, c2, 3, stride=1, padding=1), nn.ReLU(), nn.MaxPool2d(2, stride=2))
         for p in self.parameters():
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
@@ -397,7 +400,7 @@ class Transformer(nn.Module):
             finally:
                 eng.widen, eng.forward_only = widen, False
             B, T = padded_input.shape[0], padded_input.shape[3]
-            T4 = (T // 2) // 2
+            T4 = eng.enc_extent(T)
             mem = eng.arena['e%d.ff.y' % (eng.hp.n_enc - 1)] if eng.hp.n_enc else eng.arena['enc_in.y']
             start = self.vocab.SOS_ID if start_token < 0 else start_token      # the reference's callers pass vocab.SOS_ID
             strs_beam = None

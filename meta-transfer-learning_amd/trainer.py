@@ -419,7 +419,7 @@ class TransientTrainer():
         G = model._G
         if mdist.chunked_on():
             bounds = model._layout.group_bounds()
-            for tag in mdist.SLICE_ORDER:
+            for tag in (t for t in mdist.SLICE_ORDER if t in bounds):      # (no 'conv' group in a model without convolutions)
                 lo, hi = bounds[tag]
                 mdist.allreduce_sum_(G[lo:hi])
         else:
