@@ -432,6 +432,11 @@ int mtl_scale(void* stream, float* y, float a, const float* a_dev /*nullable: ov
 int mtl_adam_step(void* stream, float* theta, const float* G, float* m, float* v, int step, float lr, float beta1,
                   float beta2, float eps, long n);
 int mtl_sumsq(void* stream, const float* x, long n, float* out, float* workspace /* >= 4 KiB */, int mode, float arg);
+/* the clipped SGD step of the LM epoch loops (lm/main.py:273-277) in ONE pass over both buffers: theta becomes, bit for bit, what
+ * mtl_scale(g, 1, coef_dev, n) followed by mtl_axpy(theta, g, -lr, n) leaves (coef_dev NULL: coefficient 1; the product coef * g is
+ * rounded to fp32 before the update), g is set to zero, and -- when both pointers are given -- loss_acc[0] += loss[0] in fp32 by one
+ * thread.  theta, g 16-byte aligned, any n >= 1.  -22 for a null theta or g, n < 1 or a misaligned buffer. */
+int mtl_sgd_clip_step(void* stream, float* theta, float* g, float lr, const float* coef_dev, long n, const float* loss, float* loss_acc);
 
 /* ---- spectrogram front-end (utils/data_loader.py:65-96): after the STFT has been computed as
  * mtl_gemm_f32(frames (T x n_fft, lda = hop: overlapping rows of the padded waveform) . windowed DFT basis (n_fft x 2F)),
@@ -678,6 +683,15 @@ int mtl_lm_switch_keys(void* stream, const long* ids, const long* target, const 
 long mtl_nll_key_sum_workspace(int R, int nkey);
 int mtl_nll_key_sum(void* stream, const float* row_nll, const int* key, int seg_rows, int R, int nkey, double* sum, int* count, void* ws,
                     long ws_bytes);
+
+/* ---- LM epoch training (csrc/mtl_lstm.hip; lm/main.py:256-277): mtl_embed_bwd's occurrence chains of every window of a stream ---------
+ * ids (S, B) int64, batchified.  Windows start at i = 0, bptt, ... < S - 1; window i has T = min(bptt, S - 1 - i) steps and R = T B rows
+ * in (t, b) order at flat offset i B.  For row r of a window: first[i B + r] = 1 iff no earlier row of the SAME window holds the same id,
+ * else 0; next[i B + r] = the window-relative index of the next row of the same window with the same id, or -1.  Chains never cross a
+ * window; first and next hold (S - 1) B ints each.  One launch, a workgroup per window.  -22 before any launch for a window of more than
+ * mtl_lm_window_chains_max_rows() rows, S < 2, B < 1, bptt < 1 or a null pointer. */
+int mtl_lm_window_chains_max_rows(void);
+int mtl_lm_window_chains(void* stream, const long* ids, long S, int B, int bptt, int* first, int* next);
 
 /* ---- device-resident beam search (csrc/mtl_beam.hip; modules/decoder.py:187-291 Decoder.beam_search) --------------------------
  * A chunk of U utterances is searched at once: W hypothesis rows per utterance, row u W + r of every (U W, ...) operand.

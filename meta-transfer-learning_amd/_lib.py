@@ -119,6 +119,7 @@ SIGNATURES = {
     'mtl_scale': (I, [P, P, F, P, L]),
     'mtl_adam_step': (I, [P, P, P, P, P, I, F, F, F, F, L]),
     'mtl_sumsq': (I, [P, P, L, P, P, I, F]),
+    'mtl_sgd_clip_step': (I, [P, P, P, F, P, L, P, P]),
     'mtl_spect_logmag': (I, [P, P, I, I, I, P, P, I]),
     'mtl_spect_batch_workspace': (L, [L, I, I]),
     'mtl_spect_batch': (I, [P, P, P, I, I, I, P, I, I, P, I, I, P, L]),
@@ -159,6 +160,8 @@ SIGNATURES = {
     'mtl_lm_switch_keys': (I, [P, P, P, P, L, I, I, P]),
     'mtl_nll_key_sum_workspace': (L, [I, I]),
     'mtl_nll_key_sum': (I, [P, P, P, I, I, I, P, P, P, L]),
+    'mtl_lm_window_chains_max_rows': (I, []),
+    'mtl_lm_window_chains': (I, [P, P, L, I, I, P, P]),
     'mtl_beam_state_words': (L, [I, I, I]),
     'mtl_beam_rank': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I]),
     'mtl_beam_gather': (I, [P, P, I, P, P, L, I, I, I, L]),

@@ -77,6 +77,40 @@ __global__ void scale_kernel(float* __restrict__ y, float a, const float* a_dev,
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] *= a;
 }
 
+// clipped SGD step of the LM epoch loops in ONE pass: what scale_kernel(g, coef) followed by axpy_kernel(theta, g, -lr) leaves in theta,
+// bit for bit -- the product coef * g is rounded to fp32 on its own (__fmul_rn is never contracted into the update), and the update is
+// written as axpy_kernel writes it, so that the compiler forms it the same way -- and g = 0 for the next window.  Thread 0 of block 0
+// adds the window's loss to the running sum (one thread, fp32, stream order: no atomics).
+__global__ void sgd_clip_step_kernel(float* __restrict__ th, float* __restrict__ g, float a, const float* __restrict__ coef_dev, long n,
+                                     const float* __restrict__ loss, float* __restrict__ loss_acc) {
+    const float c = coef_dev ? *coef_dev : 1.f;
+    const long n4 = n / 4, stride = (long)gridDim.x * blockDim.x;
+    float4* th4 = reinterpret_cast<float4*>(th);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 u = th4[i];
+        float4 v = g4[i];
+        v.x = __fmul_rn(v.x, c);
+        v.y = __fmul_rn(v.y, c);
+        v.z = __fmul_rn(v.z, c);
+        v.w = __fmul_rn(v.w, c);
+        u.x += a * v.x;
+        u.y += a * v.y;
+        u.z += a * v.z;
+        u.w += a * v.w;
+        th4[i] = u;
+        g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (blockIdx.x == 0) {
+        for (long i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
+            const float v = __fmul_rn(g[i], c);
+            th[i] += a * v;
+            g[i] = 0.f;
+        }
+        if (threadIdx.x == 0 && loss && loss_acc) loss_acc[0] += loss[0];
+    }
+}
+
 // torch.optim.Adam (defaults, no amsgrad / weight decay): denom = sqrt(v)/sqrt(bc2) + eps ; theta -= lr/bc1 * m/denom
 __global__ void adam_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             float lr, float b1, float b2, float eps, float bc1, float sqrt_bc2, long n) {
@@ -1162,6 +1196,15 @@ int mtl_axpy(void* stream, float* y, const float* x, float a, long n) {
     if (!y || !x || n <= 0) return MTL_EINVAL;
     if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) return MTL_EINVAL;
     hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, as_stream(stream), y, x, a, n);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
+
+int mtl_sgd_clip_step(void* stream, float* theta, float* g, float lr, const float* coef_dev, long n, const float* loss, float* loss_acc) {
+    if (!theta || !g || n <= 0) return MTL_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(g)) & 15) return MTL_EINVAL;
+    hipLaunchKernelGGL(sgd_clip_step_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, as_stream(stream), theta, g, -lr, coef_dev,
+                       n, loss, loss_acc);
     MTL_CHECK_LAUNCH();
     return MTL_OK;
 }

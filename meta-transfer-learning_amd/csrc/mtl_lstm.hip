@@ -910,9 +910,55 @@ __global__ __launch_bounds__(256) void nll_key_merge_kernel(const double* __rest
     count[k] = c;
 }
 
+// The occurrence chains (mtl_embed_bwd's first / next) of EVERY bptt window of a batchified (S, B) stream in one launch: a workgroup
+// per window, the window's ids in LDS, per row a scan back to the window's start (first) and forward to its end (next).  Exact and
+// quadratic in the window's rows -- it runs once per stream, not once per step.
+constexpr int CHAIN_MAX_ROWS = 4096;      // 32 KiB of ids in LDS
+
+__global__ __launch_bounds__(256) void lm_window_chains_kernel(const long* __restrict__ ids, long S, int B, int bptt, int* __restrict__ first,
+                                                              int* __restrict__ next) {
+    extern __shared__ long wid[];
+    const long i0 = (long)blockIdx.x * bptt;
+    const long T = min((long)bptt, S - 1 - i0);
+    const int R = (int)(T * B);               // <= CHAIN_MAX_ROWS (checked by the host)
+    const long base = i0 * B;                 // base + R <= (S - 1) B: inside ids, first and next
+    for (int r = threadIdx.x; r < R; r += 256) wid[r] = ids[base + r];
+    __syncthreads();
+    for (int r = threadIdx.x; r < R; r += 256) {
+        const long v = wid[r];
+        int f = 1, nx = -1;
+        for (int j = r - 1; j >= 0; --j)
+            if (wid[j] == v) {
+                f = 0;
+                break;
+            }
+        for (int j = r + 1; j < R; ++j)
+            if (wid[j] == v) {
+                nx = j;
+                break;
+            }
+        first[base + r] = f;
+        next[base + r] = nx;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int mtl_lm_window_chains_max_rows(void) { return CHAIN_MAX_ROWS; }
+
+int mtl_lm_window_chains(void* stream, const long* ids, long S, int B, int bptt, int* first, int* next) {
+    if (!ids || !first || !next || S < 2 || B < 1 || bptt < 1) return MTL_EINVAL;
+    const long T = S - 1 < bptt ? S - 1 : (long)bptt;      // the longest window
+    if (T * B > CHAIN_MAX_ROWS) return MTL_EINVAL;
+    const long W = (S - 1 + bptt - 1) / bptt;
+    if (W > 0x7fffffffL) return MTL_EINVAL;
+    hipLaunchKernelGGL(lm_window_chains_kernel, dim3((unsigned)W), dim3(256), (size_t)(T * B) * sizeof(long), as_stream(stream), ids, S, B, bptt,
+                       first, next);
+    MTL_CHECK_LAUNCH();
+    return MTL_OK;
+}
 
 int mtl_lm_switch_keys(void* stream, const long* ids, const long* target, const unsigned char* lang, long eos_id, int R, int V, int* key) {
     if (!ids || !target || !lang || !key || R < 1 || V < 1) return MTL_EINVAL;

@@ -18,7 +18,12 @@
 * `LMEngine.evaluate`, `evaluate`, `evaluate_test`: validation / test loss of a batchified stream and the losses by language
   transition (lm/test.py:189-368), windows chunked into one recurrent call, sums in fp64 on the device (DESIGN.md section 18);
   `LMMetaTrainer.train(valid_interval=...)` evaluates periodically, anneals lr, stops early and saves.
-* `Dictionary`, `Corpus`, `batchify`: lm/util/data.py:69-195; `save_lm_checkpoint`: the file lmscore.LM loads for rescoring.
+* `LMTrainer`: epoch training on one corpus (lm/main.py:244-333) and, on a loaded model, fine-tuning (lm/finetune.py:266-378);
+  `LMJointTrainer`: the joint baseline (lm/main_joint.py:267-379), as written (`reference_zero_grad=True`: only the last task's
+  gradient reaches the step) or accumulating; both step with mtl_sumsq + ONE mtl_sgd_clip_step and take the occurrence chains of a
+  whole stream from ONE mtl_lm_window_chains launch.  Single rank only.
+* `Dictionary`, `Corpus`, `batchify`: lm/util/data.py:69-195; `save_lm_checkpoint`: the file lmscore.LM loads for rescoring;
+  `load_lm_checkpoint`: that file back into a trainable model and its dictionary.
 No CPU fallback: without a GPU / the built library every compute call raises.
 """
 import ctypes
@@ -184,10 +189,12 @@ class LMEngine:
         nxt[order[:-1]] = torch.where(same[1:], order[1:], torch.full_like(order[1:], -1)).to(torch.int32)
         return torch.stack([first, nxt])
 
-    def forward(self, theta, x, y, hidden, dropout_p=0.0):
+    def forward(self, theta, x, y, hidden, dropout_p=0.0, chains=None, loss_out=None):
         """x (T, B) int64, y (T*B) int64 or None, hidden (h, c) each (L, B, H) -- for a GRU the single tensor h.  -> dict(logits
-        (T*B, V), loss (1,) or None, hidden (detached new state, in the form it came in))."""
-        rec = self._recurrent(theta, x, hidden, dropout_p)
+        (T*B, V), loss (1,) or None, hidden (detached new state, in the form it came in)).  chains: None, or a (2, T*B) int32 device
+        view holding what _chains(x) gives (a slice of the trainers' chain_table()): _chains is then not run.  loss_out: None, or a (1,)
+        fp32 device tensor the loss is written to instead of the engine's own buffer."""
+        rec = self._recurrent(theta, x, hidden, dropout_p, chains=chains)
         m, lib, st = self.m, self.lib, self.stream
         T, B, xin = rec['T'], rec['B'], rec['last']
         R, H, V = T * B, m.nhid, m.ntoken
@@ -199,7 +206,8 @@ class LMEngine:
         if y is not None:
             gold = self.buf('gold', (R,), torch.int64)
             gold.copy_(y.detach().reshape(-1).to(torch.int64), non_blocking=True)
-            lse, hyp, rowloss, loss = self.buf('lse', (R,)), self.buf('hyp', (R,), torch.int64), self.buf('rowloss', (R,)), self.buf('loss', (1,))
+            lse, hyp, rowloss = self.buf('lse', (R,)), self.buf('hyp', (R,), torch.int64), self.buf('rowloss', (R,))
+            loss = self.buf('loss', (1,)) if loss_out is None else loss_out
             check(lib.mtl_ce_argmax_fwd(st, logits.data_ptr(), gold.data_ptr(), R, V, V, -1, 0.0, R, None, lse.data_ptr(), hyp.data_ptr(),
                                         rowloss.data_ptr(), loss.data_ptr()), 'ce_fwd')     # nn.CrossEntropyLoss(): mean over all T*B rows
         self.saved = dict(theta=theta, **rec)
@@ -311,10 +319,10 @@ class LMEngine:
             res['row_logp'] = row.view(S - 1, B).clone()
         return res
 
-    def _recurrent(self, theta, x, hidden, dropout_p, for_backward=True):
+    def _recurrent(self, theta, x, hidden, dropout_p, for_backward=True, chains=None):
         """the recurrent half of forward(): embedding (+ dropout) and the LSTM stack over x (T, B) from `hidden` -> dict with the top
         layer's (dropped) output `last` (T B, H) and what backward() needs (for_backward=False: without the occurrence chains of the
-        embedding scatter-add, which only backward() reads)"""
+        embedding scatter-add, which only backward() reads; chains=(2, T B) int32 on the device: taken as they are)"""
         m, lib, st = self.m, self.lib, self.stream
         T, B = int(x.shape[0]), int(x.shape[1])
         R, H, E, V, NL = T * B, m.nhid, m.ninp, m.ntoken, m.nlayers
@@ -326,8 +334,10 @@ class LMEngine:
         xh = x.detach().to(torch.int64).contiguous()
         ids = self.buf('ids', (R,), torch.int64)
         ids.copy_(xh.reshape(-1), non_blocking=True)
-        chains = None
-        if for_backward:
+        if chains is not None:
+            if tuple(chains.shape) != (2, R) or chains.dtype != torch.int32 or chains.device != theta.device or chains.stride(1) != 1:
+                raise ValueError('chains must be a (2, T*B) int32 view on the device with contiguous rows')
+        elif for_backward:
             chains = self.buf('chains', (2, R), torch.int32)
             chains.copy_(self._chains(xh), non_blocking=True)
         sc = 1.0 / (1.0 - dropout_p) if dropout_p > 0 else 1.0
@@ -674,48 +684,293 @@ class LMMetaTrainer:
         n = len(dataset.task_list)
         mine = mdist.shard_tasks(n, rank, world)
         dev = self.model.flat_parameters.device
-        if valid_interval is not None:
-            if int(valid_interval) < 1 or val_data is None:
-                raise ValueError('train(valid_interval=...) needs a positive interval and val_data')
-            if save_path is not None and dictionary is None:
-                raise ValueError('train(save_path=...) needs the dictionary the checkpoint carries')
-            val_data = val_data.to(dev)
-            test_data = test_data.to(dev) if test_data is not None else None
-        bptt = eval_bptt or dataset.bptt
-        best, counter, evaluations, stopped = None, 0, [], False
-        total, t0 = 0.0, time.time()
-        self.model.train()
-        for it in range(start_it, num_it):
+
+        def step(it):
             _, _, vx, vy = dataset.sample(-1, it)
             batches = [dataset.sample(i, it)[:2] for i in mine]
             loss, _ = self.run_iteration([(x.to(dev), y.to(dev)) for x, y in batches], (vx.to(dev), vy.to(dev)), n, mine)
-            total += mdist.allreduce_scalars([loss], dev)[0]
-            if it % log_interval == 0 and it > 0 and rank == 0:
-                cur = total / (log_interval if valid_interval is None else (it % valid_interval or valid_interval))
-                print('| it {:3d} | lr {:02.2f} | ms/batch {:5.2f} | word_loss {:5.2f} | avg ppl {:8.2f}'.format(
-                    it, self.lr, (time.time() - t0) * 1000 / log_interval, cur, math.exp(min(cur, 50.0))))
+            return mdist.allreduce_scalars([loss], dev)[0]
+
+        return _iteration_loop(self, step, start_it, num_it, log_interval, valid_interval, val_data, test_data, save_path, dictionary,
+                               eval_bptt or dataset.bptt, patience)
+
+
+def _iteration_loop(trainer, step, start_it, num_it, log_interval, valid_interval, val_data, test_data, save_path, dictionary, bptt,
+                    patience):
+    """What LMMetaTrainer.train and LMJointTrainer.train share (lm/main_meta_transfer.py:370-411 = lm/main_joint.py:338-379): the
+    iterations `step(it) -> logged loss` with the running-loss line, the periodic evaluation, annealing of trainer.lr, saving and
+    early stopping -- documented at LMMetaTrainer.train."""
+    rank = mdist.rank()
+    model = trainer.model
+    dev = model.flat_parameters.device
+    if valid_interval is not None:
+        if int(valid_interval) < 1 or val_data is None:
+            raise ValueError('train(valid_interval=...) needs a positive interval and val_data')
+        if save_path is not None and dictionary is None:
+            raise ValueError('train(save_path=...) needs the dictionary the checkpoint carries')
+        val_data = val_data.to(dev)
+        test_data = test_data.to(dev) if test_data is not None else None
+    best, counter, evaluations, stopped = None, 0, [], False
+    total, t0 = 0.0, time.time()
+    model.train()
+    for it in range(start_it, num_it):
+        total += step(it)
+        if it % log_interval == 0 and it > 0 and rank == 0:
+            cur = total / (log_interval if valid_interval is None else (it % valid_interval or valid_interval))
+            print('| it {:3d} | lr {:02.2f} | ms/batch {:5.2f} | word_loss {:5.2f} | avg ppl {:8.2f}'.format(
+                it, trainer.lr, (time.time() - t0) * 1000 / log_interval, cur, math.exp(min(cur, 50.0))))
+            t0 = time.time()
+            if valid_interval is None:
+                total = 0.0
+        if valid_interval is None or it % valid_interval != 0 or it == 0:
+            continue
+        val = evaluate(model, val_data, bptt)
+        test = evaluate(model, test_data, bptt) if test_data is not None else None
+        if rank == 0:
+            print('it {} | val loss {:5f} | ppl {:5f}'.format(it, val, math.exp(min(val, 50.0))))
+            if test is not None:
+                print('it {} | test loss {:5f} | ppl {:5f}'.format(it, test, math.exp(min(test, 50.0))))
+        best, counter, trainer.lr, save, stop = anneal_step(best, counter, trainer.lr, val, patience)
+        if save and save_path is not None and rank == 0:
+            save_lm_checkpoint(model, dictionary, save_path)
+        evaluations.append((it, val, test, trainer.lr))
+        total = 0.0
+        if stop:
+            stopped = True
+            break
+    if valid_interval is None:
+        return None
+    return dict(best_val_loss=best, evaluations=evaluations, stopped_early=stopped)
+
+
+def window_schedule(S, bptt):
+    """[(i, T)] of lm/main.py:256-258 for a batchified stream of S rows: windows start at i = 0, bptt, ... < S - 1 and have
+    T = min(bptt, S - 1 - i) steps (the last one is shorter, down to T = 1)."""
+    S, bptt = int(S), int(bptt)
+    if S < 2 or bptt < 1:
+        raise ValueError('a stream needs S >= 2 rows and bptt >= 1')
+    return [(i, min(bptt, S - 1 - i)) for i in range(0, S - 1, bptt)]
+
+
+def _single_rank(what):
+    if mdist.world_size() > 1:
+        raise NotImplementedError('%s under several ranks: one stream with one chained hidden state cannot be sharded over tasks '
+                                  '(splitting the batch columns over ranks is not built)' % what)
+
+
+class _ClippedSGD:
+    """What LMTrainer and LMJointTrainer share: the flat gradient (zero between steps), the step mtl_sumsq (mode 2) +
+    mtl_sgd_clip_step, the running loss on the device and the occurrence-chain tables of the streams trained on."""
+
+    def __init__(self, model, lr, clip):
+        _single_rank(type(self).__name__)
+        self.model, self.lr, self.clip = model, lr, clip
+        th = model.flat_parameters
+        self.g = torch.zeros_like(th)
+        self.coef = torch.empty(1, dtype=torch.float32, device=th.device)
+        self.clip_ws = torch.empty(2048, dtype=torch.float32, device=th.device)
+        self.loss_acc = torch.zeros(1, dtype=torch.float32, device=th.device)
+        self._tables = {}
+
+    def _step(self, loss):
+        """clip (skipped when self.clip is falsy) and theta <- theta - lr g; g = 0; loss_acc += loss ((1,) fp32 on the device or None)"""
+        lib, th = _lib.lib(), self.model.flat_parameters
+        st = torch.cuda.current_stream(th.device).cuda_stream
+        if self.clip:
+            check(lib.mtl_sumsq(st, self.g.data_ptr(), self.g.numel(), self.coef.data_ptr(), self.clip_ws.data_ptr(), 2, float(self.clip)),
+                  'mtl_sumsq')
+        check(lib.mtl_sgd_clip_step(st, th.data_ptr(), self.g.data_ptr(), float(self.lr), self.coef.data_ptr() if self.clip else None,
+                                    th.numel(), loss.data_ptr() if loss is not None else None,
+                                    self.loss_acc.data_ptr() if loss is not None else None), 'mtl_sgd_clip_step')
+
+    def chain_table(self, source, bptt, slot=0):
+        """(2, (S - 1) B) int32: mtl_lm_window_chains over the whole stream `source` ((S, B) int64, contiguous, on the device), kept
+        under `slot` while the same tensor (unmodified) comes back; None for a stream whose windows exceed the kernel's cap -- the
+        engine then builds each window's chains itself."""
+        lib = _lib.lib()
+        S, B = int(source.shape[0]), int(source.shape[1])
+        if min(int(bptt), S - 1) * B > int(lib.mtl_lm_window_chains_max_rows()):
+            return None
+        key = (source.data_ptr(), S, B, int(bptt), source._version)
+        ent = self._tables.get(slot)
+        if ent is not None and ent[0] is source and ent[1] == key:
+            return ent[2]
+        table = torch.empty(2, (S - 1) * B, dtype=torch.int32, device=source.device)
+        check(lib.mtl_lm_window_chains(torch.cuda.current_stream(source.device).cuda_stream, source.data_ptr(), S, B, int(bptt),
+                                       table[0].data_ptr(), table[1].data_ptr()), 'mtl_lm_window_chains')
+        self._tables[slot] = (source, key, table)
+        return table
+
+
+class LMTrainer(_ClippedSGD):
+    """Epoch training on one corpus: the loop of lm/main.py:244-333, which lm/finetune.py:266-378 repeats on a loaded model
+    (fine-tuning = load_lm_checkpoint -> LMTrainer(model, ...).train(...)).  Per window: forward at theta from the carried
+    (detached) hidden state with the model's dropout, mean cross-entropy, backward, clip with min(1, clip / (|g| + 1e-6)) (skipped
+    when `clip` is falsy), theta <- theta - lr g.  On the device a window is LMEngine.forward / backward, mtl_sumsq (mode 2) and ONE
+    mtl_sgd_clip_step (scale + update + zeroing of g + the running loss); the occurrence chains of all windows come from ONE
+    mtl_lm_window_chains launch per stream.  No device value is read on the host between two log points."""
+
+    def __init__(self, model, lr=20.0, clip=0.25, bptt=35):
+        super().__init__(model, lr, clip)
+        self.bptt = int(bptt)
+
+    def train_epoch(self, train_data, epoch=1, log_interval=200):
+        """One pass over `train_data`, a batchified (S, B) int64 stream on the model's device, in windows window_schedule(S, bptt).
+        model.train(); the hidden state is zero at the start and carried.  The running loss is an fp32 sum on the device, read (one
+        host sync, after check_handoff()) at batch % log_interval == 0 and batch > 0, divided by log_interval -- the first interval
+        holds log_interval + 1 losses, as in the reference -- printed in the reference's format and reset.
+        -> dict(windows, losses (W,) fp32 on the device, hidden)"""
+        _single_rank('LMTrainer')
+        m = self.model
+        eng = m._need_engine()
+        theta = m.flat_parameters
+        dev = theta.device
+        if train_data.dim() != 2 or train_data.device != dev or train_data.dtype != torch.int64:
+            raise ValueError("train_data must be a batchified (S, B) int64 stream on the model's device")
+        src = train_data if train_data.is_contiguous() else train_data.contiguous()
+        S, B = int(src.shape[0]), int(src.shape[1])
+        sched = window_schedule(S, self.bptt)
+        table = self.chain_table(src, self.bptt)
+        m.train()
+        p = m.dropout_rate
+        hidden = m.init_hidden(B)
+        losses = torch.zeros(len(sched), dtype=torch.float32, device=dev)
+        self.g.zero_()
+        self.loss_acc.zero_()
+        t0 = time.time()
+        for batch, (i, T) in enumerate(sched):
+            loss = losses[batch:batch + 1]
+            out = eng.forward(theta, src[i:i + T], src[i + 1:i + 1 + T].reshape(-1), hidden, p,
+                              chains=table[:, i * B:(i + T) * B] if table is not None else None, loss_out=loss)
+            hidden = out['hidden']
+            eng.backward(self.g, 1.0)
+            self._step(loss)
+            if batch % log_interval == 0 and batch > 0:
+                eng.check_handoff()
+                cur = float(self.loss_acc) / log_interval
+                print('| epoch {:3d} | {:5d}/{:5d} batches | lr {:02.2f} | ms/batch {:5.2f} | word_loss {:5.2f} | ppl {:8.2f}'.format(
+                    epoch, batch, S // self.bptt, self.lr, (time.time() - t0) * 1000 / log_interval, cur, math.exp(min(cur, 50.0))))
+                self.loss_acc.zero_()
                 t0 = time.time()
-                if valid_interval is None:
-                    total = 0.0
-            if valid_interval is None or it % valid_interval != 0 or it == 0:
-                continue
-            val = evaluate(self.model, val_data, bptt)
-            test = evaluate(self.model, test_data, bptt) if test_data is not None else None
-            if rank == 0:
-                print('it {} | val loss {:5f} | ppl {:5f}'.format(it, val, math.exp(min(val, 50.0))))
-                if test is not None:
-                    print('it {} | test loss {:5f} | ppl {:5f}'.format(it, test, math.exp(min(test, 50.0))))
+        torch.cuda.synchronize(dev)
+        eng.check_handoff()
+        return dict(windows=len(sched), losses=losses, hidden=hidden)
+
+    def train(self, train_data, val_data, epochs, test_data=None, save_path=None, dictionary=None, eval_bptt=None, patience=5,
+              log_interval=200):
+        """lm/main.py:292-336 (lm/finetune.py:330-378): per epoch train_epoch, then the loss of `val_data` (and of `test_data` if
+        given; windows of eval_bptt or self.bptt) with the reference's end-of-epoch lines; `anneal_step` decides -- a first or better
+        validation loss is saved to `save_path` with save_lm_checkpoint(model, dictionary, save_path), any other divides self.lr by 4
+        -- and the loop stops after `patience` non-improvements in a row.  After the loop the best checkpoint's parameters (if one was
+        saved) are loaded back into the model in place, and validation and test are evaluated once more.  A `dictionary` whose size
+        is not model.ntoken (a corpus that added words to a loaded model's dictionary) raises ValueError before any training.
+        -> dict(best_val_loss, epochs [(epoch, val, test or None, lr after the decision)], stopped_early, final_val, final_test)"""
+        _single_rank('LMTrainer')
+        m = self.model
+        if save_path is not None and dictionary is None:
+            raise ValueError('train(save_path=...) needs the dictionary the checkpoint carries')
+        if dictionary is not None and len(dictionary) != m.ntoken:
+            raise ValueError('the dictionary holds %d words, the model %d: a corpus that adds words cannot train this model'
+                             % (len(dictionary), m.ntoken))
+        dev = m.flat_parameters.device
+        train_data, val_data = train_data.to(dev), val_data.to(dev)
+        test_data = test_data.to(dev) if test_data is not None else None
+        bptt = eval_bptt or self.bptt
+        best, counter, log, stopped, saved = None, 0, [], False, False
+        for epoch in range(1, int(epochs) + 1):
+            t0 = time.time()
+            self.train_epoch(train_data, epoch, log_interval)
+            val = evaluate(m, val_data, bptt)
+            test = evaluate(m, test_data, bptt) if test_data is not None else None
+            print('-' * 89 + '\n' + '| end of epoch {:3d} | time: {:5.2f}s | valid loss {:5.2f} | valid ppl {:8.2f}'.format(
+                epoch, time.time() - t0, val, math.exp(min(val, 50.0))) + '-' * 89)
+            if test is not None:
+                print('-' * 89 + '\n' + '| end of epoch {:3d} | time: {:5.2f}s | test loss {:5.2f} | test ppl {:8.2f}'.format(
+                    epoch, time.time() - t0, test, math.exp(min(test, 50.0))) + '-' * 89)
             best, counter, self.lr, save, stop = anneal_step(best, counter, self.lr, val, patience)
-            if save and save_path is not None and rank == 0:
-                save_lm_checkpoint(self.model, dictionary, save_path)
-            evaluations.append((it, val, test, self.lr))
-            total = 0.0
+            if save and save_path is not None:
+                save_lm_checkpoint(m, dictionary, save_path)
+                saved = True
+            log.append((epoch, val, test, self.lr))
             if stop:
                 stopped = True
                 break
-        if valid_interval is None:
-            return None
-        return dict(best_val_loss=best, evaluations=evaluations, stopped_early=stopped)
+        if saved:
+            state = torch.load(save_path, map_location='cpu', weights_only=False)['model_state_dict']
+            with torch.no_grad():
+                for name, prm in m.named_parameters():
+                    prm.copy_(state[name])
+        final_val = evaluate(m, val_data, bptt)
+        final_test = evaluate(m, test_data, bptt) if test_data is not None else None
+        print('=' * 89 + '| End of training | val loss {:5.2f} | val ppl {:8.2f}'.format(final_val, math.exp(min(final_val, 50.0))) + '=' * 89)
+        if final_test is not None:
+            print('=' * 89 + '| End of training | test loss {:5.2f} | test ppl {:8.2f}'.format(final_test, math.exp(min(final_test, 50.0)))
+                  + '=' * 89)
+        return dict(best_val_loss=best, epochs=log, stopped_early=stopped, final_val=final_val, final_test=final_test)
+
+
+class LMJointTrainer(_ClippedSGD):
+    """The joint baseline of lm/main_joint.py:267-379: per iteration every task's batch through ONE model, each task's forward from
+    the hidden state the previous task's forward returned (one `hidden` threads through all tasks and all iterations), losses
+    weighted with task_weights(n, ratio), then one clip and one SGD step with lr.  The logged loss is sum_i w_i L_i.
+
+    reference_zero_grad is a choice of SEMANTICS, not of speed.  True reproduces the reference as written: its forward_one_batch
+    calls model.zero_grad() before EVERY task's forward (lm/main_joint.py:271), so when the optimiser steps (:336) only the LAST
+    task's weighted gradient is left -- the earlier tasks contribute their loss to the log and their hidden state to the chain, and
+    nothing to the update; their backward is therefore not run.  False accumulates G = sum_i w_i g_i, the evident intent."""
+
+    def __init__(self, model, lr=20.0, clip=0.25, ratio=0.8, reference_zero_grad=True):
+        super().__init__(model, lr, clip)
+        self.ratio, self.reference_zero_grad = ratio, bool(reference_zero_grad)
+        self.hidden = None
+
+    def run_iteration(self, task_batches, chains=None):
+        """task_batches: [(x (T, B), y (T*B))] in task order; chains: None or per task None / the (2, T*B) slice of chain_table().
+        -> (sum_i w_i L_i, [L_i])   (single device sync at the end)"""
+        _single_rank('LMJointTrainer')
+        m = self.model
+        eng = m._need_engine()
+        theta = m.flat_parameters
+        n = len(task_batches)
+        w = task_weights(n, self.ratio)
+        p = m.dropout_rate if m.training else 0.0
+        if self.hidden is None:
+            self.hidden = m.init_hidden(task_batches[0][0].shape[1])
+        losses = torch.zeros(n, dtype=torch.float32, device=theta.device)
+        for i, (x, y) in enumerate(task_batches):
+            out = eng.forward(theta, x, y, self.hidden, p, chains=chains[i] if chains is not None else None, loss_out=losses[i:i + 1])
+            self.hidden = out['hidden']
+            if i == n - 1 or not self.reference_zero_grad:
+                eng.backward(self.g, w[i])
+        self._step(None)
+        torch.cuda.synchronize(theta.device)
+        eng.check_handoff()
+        host = [float(v) for v in losses.cpu()]
+        return sum(wi * li for wi, li in zip(w, host)), host
+
+    def train(self, dataset, start_it, num_it, log_interval=200, valid_interval=None, val_data=None, test_data=None, save_path=None,
+              dictionary=None, eval_bptt=None, patience=5):
+        """loop of lm/main_joint.py:275-379: per iteration every task's batch `dataset.sample(i, it)[:2]`; the running-loss line, the
+        periodic evaluation, annealing, saving and stopping are LMMetaTrainer.train's (the same code).
+        -> None without valid_interval, else dict(best_val_loss, evaluations, stopped_early)"""
+        _single_rank('LMJointTrainer')
+        dev = self.model.flat_parameters.device
+        n, bptt = len(dataset.task_list), dataset.bptt
+        streams = [t.to(dev).contiguous() for t in dataset.task_list]
+
+        def step(it):
+            batches, chains = [], []
+            for i in range(n):
+                S, B = int(streams[i].shape[0]), int(streams[i].shape[1])
+                off = ((it * bptt) % S) - (((it * bptt) % S) % bptt)                  # LMDataset.sample's offset: a multiple of bptt
+                x, y = dataset.get_batch(streams[i], off)
+                table = self.chain_table(streams[i], bptt, slot=i)
+                batches.append((x, y))
+                chains.append(table[:, off * B:(off + int(x.shape[0])) * B] if table is not None else None)
+            return self.run_iteration(batches, chains)[0]
+
+        return _iteration_loop(self, step, start_it, num_it, log_interval, valid_interval, val_data, test_data, save_path, dictionary,
+                               eval_bptt or bptt, patience)
 
 
 def anneal_step(best, counter, lr, val, patience=5):
@@ -822,3 +1077,19 @@ def save_lm_checkpoint(model, dictionary, path):
     torch.save(dict(model_state_dict=state, word2idx=dictionary.word2idx, idx2word=dictionary.idx2word,
                     ntoken=int(model.encoder.weight.size(0)), ninp=int(model.encoder.weight.size(1)), nhid=model.nhid,
                     nlayers=model.nlayers, dropout=model.drop.p, tie_weights=bool(model.tie_weights), rnn_type=model.rnn_type), path)
+
+
+def load_lm_checkpoint(path, cuda=True):
+    """save_lm_checkpoint's file (the form of lm/convert.py:431-446) back into a trainable model: an RNNModel of the saved rnn_type
+    ('LSTM' when the key is missing, as in the reference's files) with the saved tie_weights, ntoken, ninp, nhid, nlayers and dropout,
+    its state loaded strictly, and a Dictionary of the saved word2idx / idx2word.  ValueError when the dictionary's size is not
+    ntoken.  -> (model, dictionary); cuda=True moves the model to the device (the product path), False leaves it on the host."""
+    ck = torch.load(path, map_location='cpu', weights_only=False)
+    dictionary = Dictionary()
+    dictionary.word2idx, dictionary.idx2word = dict(ck['word2idx']), dict(ck['idx2word'])
+    if len(dictionary) != int(ck['ntoken']) or len(dictionary.word2idx) != int(ck['ntoken']):
+        raise ValueError('checkpoint %s: its dictionary holds %d words, its model %d' % (path, len(dictionary), int(ck['ntoken'])))
+    model = RNNModel(ck.get('rnn_type', 'LSTM'), int(ck['ntoken']), int(ck['ninp']), int(ck['nhid']), int(ck['nlayers']),
+                     float(ck['dropout']), bool(ck['tie_weights']))
+    model.load_state_dict(ck['model_state_dict'], strict=True)
+    return (model.cuda() if cuda else model), dictionary
