@@ -538,6 +538,24 @@ int mtl_fbank_slots(void);
 int mtl_fbank_batch(void* stream, const float* wav, const long* offsets, int K, int fl, int fs, int nfft, const float* basis, int ldb,
                     int nfilt, const int* band, const float* band_w, int n_w, float* out, int Tmax, int normalize, void* workspace,
                     long workspace_bytes);
+/* SpecAugment (Park et al., 2019) on the finished batch, BEHIND either feature launch (csrc/mtl_specaug.hip; frontend.SpecAugment and
+ * DESIGN.md section 23 hold the definition, tests/specaug_util.py restates it in numpy / fp64).  x: the (K, F, Tmax) fp32 batch, changed
+ * in place; table: K rows of 3 + 2 freq_masks + 2 time_masks ints on the device: tau, c, w, then (f0, f) per frequency mask, then (t0, t)
+ * per time mask.  Per utterance k, over columns [0, tau) only (columns >= tau are never written), in this order:
+ *   warp   when w != c: out[j] = x[i0] for a == 0, else fmaf(a, x[i0 + 1] - x[i0], x[i0]) in fp32, the same map for every row:
+ *          j < w: num = (2 j + 1) c - w, den = 2 w, base = 0; j >= w: num = (2 (j - w) + 1) (tau - c) - (tau - w), den = 2 (tau - w),
+ *          base = c; q = floor(num / den), r = num - q den, i0 = base + q, a = (float)((double)r / (double)den); i0 < 0: i0 = 0, a = 0;
+ *          i0 >= tau - 1: i0 = tau - 1, a = 0.  w == c: the row is neither read nor written by this step.
+ *   freq   rows [f0, f0 + f) become +0.0f over [0, tau)
+ *   time   frames [t0, t0 + t) become +0.0f in every row
+ * One launch, one workgroup per (utterance, row): a warped row is read once into LDS and written back warped and masked; a row that is not
+ * warped is never read, only its masked spans are stored.  No workspace, no atomics: bitwise repeatable.  The table lives on the device,
+ * so the kernel cannot refuse it: tau is cut to [0, Tmax], every span to the plane, and a warp with w outside [1, tau - 1] or c outside
+ * [0, tau] is left out -- a wrong table cannot read or write out of bounds.  1 <= K, 1 <= F, K F < 2^31, 1 <= Tmax <= 16384 (a row in
+ * 64 KB of LDS), 0 <= freq_masks, time_masks <= 8; null pointers and anything else return -22 before any launch. */
+#define MTL_SPECAUG_MAX_MASKS 8
+#define MTL_SPECAUG_MAX_FRAMES 16384
+int mtl_spec_augment(void* stream, float* x, int K, int F, int Tmax, const int* table, int freq_masks, int time_masks);
 
 /* ---- accent discriminator on the encoder output (joint_train.py --multitask / --adversarial) ------------------------------
  * modules/discriminator.py, trainer/asr/joint_trainer.py:29-37, utils/metrics.py:164-199 (csrc/mtl_disc.hip):

@@ -8,7 +8,7 @@ from .data import (Vocab, SyntheticTask, ManifestTaskDataset, SpectrogramDataset
                    synth_batch, is_chinese_char, is_contain_chinese_word, get_word_segments_per_language)
 from .frontend import (SpectrogramFrontEnd, LogFBankFrontEnd, fbank_geometry, fbank_frames, mel_filterbank, mel_filterbank_sparse,  # noqa: F401
                        NoiseInjection, TempoGainAugment, load_randomly_augmented_audio, tempo_gain, tempo_gain_tables, resample, resample_plan,
-                       resample_taps, resample_tables, wsola_geometry, pack_waveforms)
+                       resample_taps, resample_tables, wsola_geometry, pack_waveforms, SpecAugment)
 from .functions import (init_transformer_model, save_meta_model, load_meta_model, save_joint_model, load_joint_model,  # noqa: F401
                         post_process, compute_num_params)
 from .discriminator import (Discriminator, init_discriminator_model, save_discriminator, load_discriminator,  # noqa: F401

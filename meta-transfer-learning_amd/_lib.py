@@ -134,6 +134,7 @@ SIGNATURES = {
     'mtl_fbank_tile_frames': (I, []),
     'mtl_fbank_slots': (I, []),
     'mtl_fbank_batch': (I, [P, P, P, I, I, I, I, P, I, I, P, P, I, P, I, I, P, L]),
+    'mtl_spec_augment': (I, [P, P, I, I, I, P, I, I]),
     'mtl_disc_workspace': (L, [I, I, I]),
     'mtl_disc_fwd': (I, [P, P, I, I, I, P, P, I, I, I, P, P, P, P, L]),
     'mtl_disc_bwd': (I, [P, P, P, P, I, I, I, I, I, I, F, F, P, P, P]),

@@ -13,8 +13,8 @@ import unicodedata
 import numpy as np
 import torch
 
-from .frontend import (FBANK_EPS, RESAMPLE_MAX_RATIO, _RESAMPLE_TAPS, LogFBankFrontEnd, NoiseInjection, SpectrogramFrontEnd,  # noqa: F401
-                       TempoGainAugment, fbank_frames, fbank_geometry, load_randomly_augmented_audio, mel_filterbank, mel_filterbank_sparse,
+from .frontend import (FBANK_EPS, RESAMPLE_MAX_RATIO, _RESAMPLE_TAPS, LogFBankFrontEnd, NoiseInjection, SpecAugment, SpectrogramFrontEnd,  # noqa: F401
+                       TempoGainAugment, _cut, fbank_frames, fbank_geometry, load_randomly_augmented_audio, mel_filterbank, mel_filterbank_sparse,
                        pack_waveforms, resample, resample_plan, resample_taps, resample_tables, tempo_gain, tempo_gain_tables,
                        wsola_geometry)
 
@@ -142,7 +142,7 @@ class ManifestTaskDataset:
     `__getitem__` / `__len__` follow utils/data_loader.py:323-340 (validation / test use: manifest 0 only unless is_train)."""
 
     def __init__(self, vocab, args, manifest_filepath_list, feature_fn=None, partitions=None, seed=None, is_train=False,
-                 device_batches=False, noise=None, augment=None, resample=False):
+                 device_batches=False, noise=None, augment=None, resample=False, spec_augment=None):
         """device_batches=True: `sample()` featurises each part (train / validation) with ONE `SpectrogramFrontEnd.batch` call and
         returns `inputs` on the device (the trainers copy device-resident inputs straight into their static buffers); the sizes,
         percentages and targets stay host tensors as `collate` makes them, and the index stream is the same.  The front-end is
@@ -167,8 +167,18 @@ class ManifestTaskDataset:
         of a part to its one `batch` call; the per-utterance path (`__getitem__`, the rows of `sample()` without device_batches) sends
         an utterance whose rate differs through `batch([y], rates=[rate])`.  The augmentation and noise plans are made for the
         CONVERTED lengths; no draw is added, so the stream is the same with and without.  Not with a feature_fn (which gets paths).
-        resample=False (the default) never reads the header rate: every call and every output bit is as without the keyword."""
-        _reject_options(feature_fn, device_batches, noise is not None, augment is not None, resample)
+        resample=False (the default) never reads the header rate: every call and every output bit is as without the keyword.
+
+        spec_augment=SpecAugment(...): every utterance's finished, normalised feature plane gets a small time warp, frequency masks and
+        time masks on the device (`SpecAugment` for the definition, `BatchFrontEnd.batch(spec=)` for the launch; the reference has no
+        such stage).  Per utterance the stream yields tempo, gain, that utterance's noise draws and THEN its spec draws, a fixed number
+        of uniforms (`SpecAugment.draw`); a part that `need` leaves out consumes them too.  The plan is made for the FINAL frame counts:
+        behind rate conversion, tempo change and the cut to args.src_max_len.  The batched path hands the plan of a part to its one
+        `batch` call; the per-utterance path (`__getitem__`, the rows of `sample()` without device_batches) goes through
+        `batch([y], max_frames=args.src_max_len, spec=...)`.  Not with a feature_fn (which gets paths).  Validation loaders are built
+        without it by the caller, as with `augment`.  spec_augment=None leaves the stream and every call exactly as they are without."""
+        _reject_options(feature_fn, device_batches, noise is not None, augment is not None, resample, spec_augment is not None)
+        self._spec = spec_augment
         self._resample, self._rate = bool(resample), getattr(args, 'sample_rate', None)     # (a feature_fn needs no rate)
         self._noise = None if noise is None else (noise[0], float(noise[1]))
         self._augment = augment
@@ -208,27 +218,30 @@ class ManifestTaskDataset:
         return spects, trans
 
     def _feature(self, path, draw):
-        """per-utterance path: feature_fn(path), or for an utterance whose draw = (augmentation, noise) asks for either
-        `batch([y], augment=..., noise=...)[0][0, 0]`, handed back on the host like every feature; an utterance that `place` leaves clean
-        (longer than its noise file) and is not augmented takes the clean path"""
+        """per-utterance path: feature_fn(path), or for an utterance whose draw = (augmentation, noise[, spec]) asks for any of them
+        `batch([y], augment=..., noise=..., spec=...)[0][0, 0]`, handed back on the host like every feature; an utterance that `place`
+        leaves clean (longer than its noise file) and is neither augmented nor spec-augmented takes the clean path"""
         rate = None
         if self._resample:                                       # (a file at the front-end's own rate takes the paths below as it is)
             y, rate = load_wav_pcm16_rate(path)
             rate = None if rate == self._rate else rate
-        if rate is None and (draw is None or (draw[0] is None and draw[1] is None)):
+        if rate is None and (draw is None or all(d is None for d in draw)):
             return self.feature_fn(path)
         if not self._resample:
             y = load_wav_pcm16(path)
         kw, _ = self._plan([y.shape[0]], None if rate is None else [rate], None if draw is None else [draw])
         if not kw:
             return self.feature_fn(path)
+        if 'spec' in kw:                                         # (the plan was made for the frames behind the cut)
+            kw['max_frames'] = self.args.src_max_len
         return self._front_end().batch([y], **kw)[0][0, 0].cpu()
 
     def _plan(self, lengths, rates, draws):
         """K lengths, their K rates | None, their K draws | None -> (the keywords of `batch` for these utterances, the K final lengths).
         THE chained-length rule, for both paths: the rates change the lengths, the tempo changes them again, and the noise plan is made
         for the result -- a noise segment is as long as the converted, stretched utterance.  `noise` is left out when every utterance
-        stays clean (no noise draw, or `place` left it clean: longer than its noise file), so that such a call is the clean one."""
+        stays clean (no noise draw, or `place` left it clean: longer than its noise file), so that such a call is the clean one.  The
+        spec plan is made last, for the frames of the final lengths cut to args.src_max_len (the front-end says how many those are)."""
         kw = {}
         if rates is not None:
             kw['rates'], lengths = list(rates), resample_plan(lengths, rates, self._rate)[0]
@@ -239,17 +252,23 @@ class ManifestTaskDataset:
             noise_off, level = self._noise[0].plan([d[1] for d in draws], lengths)
             if (noise_off >= 0).any():
                 kw['noise'] = (self._noise[0], noise_off, level)
+        if draws is not None and self._spec is not None:
+            fe = self._front_end()
+            frames = _cut(fe._frame_counts(np.array(lengths, dtype=np.int64)), self.args.src_max_len)
+            kw['spec'] = self._spec.plan([d[2] for d in draws], frames, fe.F)
         return kw, lengths
 
     def _draws(self, n):
         """the draws of n utterances, in order, from the dataset's stream: per utterance (augmentation draw | None, noise draw | None),
-        tempo and gain before that utterance's noise draws (None without an augmentation and an injector)"""
-        if self._noise is None and self._augment is None:
+        tempo and gain before that utterance's noise draws (None without an augmentation, an injector and a SpecAugment); with a
+        SpecAugment (augmentation draw | None, noise draw | None, spec draws), the spec draws last"""
+        if self._noise is None and self._augment is None and self._spec is None:
             return None
         out = []
         for _ in range(n):
             aug = None if self._augment is None else self._augment.draw(self.rng)
-            out.append((aug, None if self._noise is None else self._noise[0].draw(self.rng, self._noise[1])))
+            draw = (aug, None if self._noise is None else self._noise[0].draw(self.rng, self._noise[1]))
+            out.append(draw if self._spec is None else draw + (self._spec.draw(self.rng),))
         return out
 
     def _front_end(self):
@@ -311,8 +330,8 @@ class ManifestTaskDataset:
         return self._feature(row[0], None if draws is None else draws[0])[:, :self.args.src_max_len], parse_transcript(self.vocab, row[1])
 
 
-def _reject_options(feature_fn, device_batches, noise, augment, resample):
-    """THE option rejections of every dataset here (noise, augment: whether they were asked for).  A feature_fn gets paths, not samples,
+def _reject_options(feature_fn, device_batches, noise, augment, resample, spec_augment=False):
+    """THE option rejections of every dataset here (noise, augment, spec_augment: whether they were asked for).  A feature_fn gets paths, not samples,
     so nothing that works on samples on the device goes with it; tempo and gain exist in the batched path only."""
     if device_batches and feature_fn is not None:
         raise ValueError('device_batches=True featurises with the batched device front-end: it cannot be combined with a feature_fn')
@@ -328,6 +347,9 @@ def _reject_options(feature_fn, device_batches, noise, augment, resample):
     if resample and feature_fn is not None:
         raise NotImplementedError('sample rates are converted on the device: resample=True cannot be combined with a feature_fn (which '
                                   'gets paths)')
+    if spec_augment and feature_fn is not None:
+        raise NotImplementedError('SpecAugment (spec_augment=) warps and masks the feature batch on the device: it cannot be combined with '
+                                  'a feature_fn (which gets paths)')
 
 
 class _WavDataset(ManifestTaskDataset):
@@ -336,9 +358,9 @@ class _WavDataset(ManifestTaskDataset):
     default feature_fn and the batched path (`sample()` of a part: one `batch` call of it).  `self.sample_rate` is the derived class's."""
 
     def __init__(self, make_front_end, char_lines, vocab, args, audio_conf, manifest_filepath_list, normalize, augment, input_type, is_train,
-                 partitions, feature_fn, seed, device_batches, resample):
+                 partitions, feature_fn, seed, device_batches, resample, spec_augment=None):
         noise_dir = audio_conf.get('noise_dir')
-        _reject_options(feature_fn, device_batches, noise_dir is not None, augment, resample)
+        _reject_options(feature_fn, device_batches, noise_dir is not None, augment, resample, spec_augment is not None)
         self.noiseInjector, noise = None, None
         if noise_dir is not None:
             self.noiseInjector = NoiseInjection(noise_dir, audio_conf['sample_rate'], audio_conf.get('noise_levels', (0, 0.5)))
@@ -357,7 +379,7 @@ class _WavDataset(ManifestTaskDataset):
                 return front_end()(load_wav_pcm16(path)).cpu()
         super().__init__(vocab, args, manifest_filepath_list, feature_fn=feature_fn, partitions=partitions, seed=seed, is_train=is_train)
         # behind the base constructor, for which the default feature_fn above would be a user's
-        self._noise, self._augment = noise, TempoGainAugment() if augment else None
+        self._noise, self._augment, self._spec = noise, TempoGainAugment() if augment else None, spec_augment
         self._resample, self._rate = bool(resample), self.sample_rate
         self.device_batches, self._fe_factory = device_batches, front_end
         self.manifest_filepath_list, self.input_type = manifest_filepath_list, input_type
@@ -394,17 +416,19 @@ class SpectrogramDataset(_WavDataset):
     reference too).
     device_batches=True: see ManifestTaskDataset (not part of the reference's constructor; default off).
     resample=True: files at another rate than audio_conf['sample_rate'] are converted on the device, see ManifestTaskDataset (not part of the
-    reference's constructor either, which leaves this to sox; default off, and then the header rate is never read)."""
+    reference's constructor either, which leaves this to sox; default off, and then the header rate is never read).
+    spec_augment=SpecAugment(...): time warp, frequency and time masks on the finished feature batch, see ManifestTaskDataset (the reference
+    has no such stage; default None, and then the draw stream and every call are as without the keyword)."""
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
-                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False):
+                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False, spec_augment=None):
         self.window_stride, self.window_size = audio_conf['window_stride'], audio_conf['window_size']
         self.sample_rate, self.window = audio_conf['sample_rate'], audio_conf.get('window', 'hamming')
         super().__init__(lambda: SpectrogramFrontEnd(self.sample_rate, self.window_size, self.window_stride,
                                                      self.window if self.window in ('hamming', 'hann', 'blackman', 'bartlett') else 'hamming',
                                                      self.normalize),
                          '342-361', vocab, args, audio_conf, manifest_filepath_list, normalize, augment, input_type, is_train, partitions,
-                         feature_fn, seed, device_batches, resample)
+                         feature_fn, seed, device_batches, resample, spec_augment)
         # (the reference leaves part_len at the LAST manifest's partition size, or max_size without partitions: :211-222)
         self.part_len = (max(int(len(self.ids_list[-1]) * partitions[len(self.ids_list) - 1]), 1) if partitions is not None
                          else self.max_size)
@@ -420,16 +444,17 @@ class LogFBankDataset(_WavDataset):
     80 log mel filterbank energies per frame from the device front-end (LogFBankFrontEnd at audio_conf['sample_rate']) unless a
     `feature_fn` is given.  Same attributes as the reference object (max_size = longest manifest x manifests, ids_list, input_type,
     manifest_filepath_list, normalize, vocab), the same two console lines, and its __getitem__ (manifests interleaved by index).
-    Beyond the reference: `sample()` and the keywords partitions, seed, device_batches, resample and feature_fn of the
+    Beyond the reference: `sample()` and the keywords partitions, seed, device_batches, resample, spec_augment and feature_fn of the
     ManifestTaskDataset machinery -- for one seed the index and draw stream is that of SpectrogramDataset -- and audio_conf['noise_dir'] /
     augment=True, which the reference's class accepts and ignores, work as on SpectrogramDataset, with the same rejections."""
 
     def __init__(self, vocab, args, audio_conf, manifest_filepath_list, normalize=False, augment=False, input_type='char',
-                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False):
+                 is_train=False, partitions=None, feature_fn=None, seed=None, device_batches=False, resample=False, spec_augment=None):
         self.sample_rate = audio_conf.get('sample_rate', getattr(args, 'sample_rate', 16000))
         fbank_geometry(self.sample_rate)                             # a rate beyond the 512-point transform is rejected here
         super().__init__(lambda: LogFBankFrontEnd(self.sample_rate, 80, self.normalize), '157-165', vocab, args, audio_conf,
-                         manifest_filepath_list, normalize, augment, input_type, is_train, partitions, feature_fn, seed, device_batches, resample)
+                         manifest_filepath_list, normalize, augment, input_type, is_train, partitions, feature_fn, seed, device_batches, resample,
+                         spec_augment)
         self.max_size = max(len(ids) for ids in self.ids_list) * len(self.ids_list)      # :114-122: no 30000 rule in this class
         print('max_size:', self.max_size)
         print('input_type:', input_type)

@@ -3,7 +3,8 @@
 One pipeline (`BatchFrontEnd.batch`): up to three optional stages, always in this order -- rate conversion (`resample`), tempo and gain
 (`tempo_gain`, `TempoGainAugment`), noise (`NoiseInjection`) -- and then the feature type's own launch: the spectrogram of
 SpectrogramParser.parse_audio (`SpectrogramFrontEnd`, utils/data_loader.py:65-96) or the log-mel filterbank energies of
-LogFBankDataset.parse_audio (`LogFBankFrontEnd`, utils/data_loader.py:145-155).  A stage is a small object with a host part (pure
+LogFBankDataset.parse_audio (`LogFBankFrontEnd`, utils/data_loader.py:145-155).  One more optional stage runs BEHIND that launch, on the
+finished batch: `SpecAugment` (time warp, frequency and time masks).  A stage is a small object with a host part (pure
 numpy: lengths and parameters -> tables and output lengths; the public `*_tables` / `*_plan` functions return exactly these tables)
 and a device part (stage the tables, launch on a stream).  `data.py` holds the datasets that drive this; DESIGN.md sections 10-15 the
 reasons.
@@ -542,6 +543,137 @@ class NoiseInjection(object):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Stage 4, BEHIND the feature launch: SpecAugment (Park et al., 2019; not in the reference); DESIGN.md section 23
+# ------------------------------------------------------------------------------------------------------------------
+SPECAUG_MAX_MASKS = 8                      # MTL_SPECAUG_MAX_MASKS of include/mtl_hip.h: masks of either kind per utterance
+SPECAUG_MAX_FRAMES = 16384                 # MTL_SPECAUG_MAX_FRAMES: the row of a warped utterance in 64 KB of LDS
+
+
+class SpecPlan(np.ndarray):
+    """the int32 table of `SpecAugment.plan`, (K, 3 + 2 freq_masks + 2 time_masks): an array that knows how its columns divide
+    (`freq_masks`, `time_masks`); rows taken from it (`t[k:k + 1]`, `t[k]`) know it too"""
+
+    def __new__(cls, table, freq_masks, time_masks):
+        obj = np.ascontiguousarray(table, dtype=np.int32).view(cls)
+        obj.freq_masks, obj.time_masks = int(freq_masks), int(time_masks)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.freq_masks, self.time_masks = getattr(obj, 'freq_masks', None), getattr(obj, 'time_masks', None)
+
+
+class SpecAugment(object):
+    """SpecAugment (Park et al., 2019) on the device: a small time warp of the feature planes, then `freq_masks` frequency masks, then
+    `time_masks` time masks.  Pure numpy: the device part is `BatchFrontEnd.batch(spec=)`, one launch of mtl_spec_augment behind the
+    feature launch.  The reference has no such stage and no implementation is a dependency of this project, so the behaviour is DEFINED
+    by the restatement below; tests/specaug_util.py holds it in numpy and fp64, DESIGN.md section 23 the reasons.
+
+    The stage acts on the NORMALISED batch: the statistics are those of the clean utterance (a mask does not shift the mean of what is
+    left), and the 0.0 that a mask writes IS the utterance mean -- the value the paper masks with.
+
+      draws       draw(rng): rng.random_sample(2 + 2 freq_masks + 2 time_masks) -- warp (u_c, u_d), then (u_f, u_f0) per frequency mask,
+                  then (u_t, u_t0) per time mask.  The number does not depend on the audio or on the widths (all ranks keep one stream);
+                  time_warp=0 consumes its two warp draws all the same.
+      plan        plan(draws, frames, F) -> int32 (K, 3 + 2 freq_masks + 2 time_masks): tau, c, w, (f0, f)..., (t0, t)...; tau is the
+                  utterance's OWN frame count (frames[k], behind the cut to max_frames), not Tmax; fp64 and floor throughout, W = time_warp:
+                    warp   iff W >= 1 and tau >= 2 W + 1: c = W + floor(u_c (tau - 2 W)), d = floor(u_d (2 W - 1)) - (W - 1), w = c + d
+                           (1 <= w <= tau - 2); otherwise c = w = 0: no warp
+                    freq   f = floor(u_f (freq_width + 1)), f0 = floor(u_f0 (F - f + 1))
+                    time   t = floor(u_t (min(time_width, floor(time_ratio tau)) + 1)), t0 = floor(u_t0 (tau - t + 1))
+      effect      on utterance k's plane x[F, Tmax], over columns [0, tau) only (the zero padding behind stays as it is, bit for bit),
+                  in this order:
+                    1. warp, when w != c, every row by the same map: source frame c lands on output frame w, linear on either side.
+                       Output j < w: num = (2 j + 1) c - w, den = 2 w, base = 0; j >= w: num = (2 (j - w) + 1) (tau - c) - (tau - w),
+                       den = 2 (tau - w), base = c; in integers q = floor(num / den), r = num - q den, i0 = base + q,
+                       a = (float)((double)r / (double)den); i0 < 0: i0 = 0, a = 0; i0 >= tau - 1: i0 = tau - 1, a = 0;
+                       out[j] = x[i0] when a == 0, else fmaf(a, x[i0 + 1] - x[i0], x[i0]) in fp32.  w == c leaves every bit alone.
+                    2. rows [f0, f0 + f) become 0.0 over [0, tau)
+                    3. frames [t0, t0 + t) become 0.0 in every row
+                  Masks may overlap and may be empty."""
+
+    def __init__(self, time_warp=40, freq_masks=2, freq_width=27, time_masks=2, time_width=40, time_ratio=0.2):
+        for name, v in (('time_warp', time_warp), ('freq_masks', freq_masks), ('freq_width', freq_width), ('time_masks', time_masks),
+                        ('time_width', time_width)):
+            if int(v) != v or int(v) < 0:
+                raise ValueError('SpecAugment: %s must be a non-negative integer, got %r' % (name, v))
+        if int(freq_masks) > SPECAUG_MAX_MASKS or int(time_masks) > SPECAUG_MAX_MASKS:
+            raise ValueError('SpecAugment: at most %d masks of either kind, got freq_masks=%d, time_masks=%d'
+                             % (SPECAUG_MAX_MASKS, freq_masks, time_masks))
+        if not 0.0 <= float(time_ratio) <= 1.0:
+            raise ValueError('SpecAugment: time_ratio must lie in [0, 1], got %r' % (time_ratio,))
+        self.time_warp, self.freq_masks, self.freq_width = int(time_warp), int(freq_masks), int(freq_width)
+        self.time_masks, self.time_width, self.time_ratio = int(time_masks), int(time_width), float(time_ratio)
+
+    @property
+    def n_draws(self):
+        return 2 + 2 * self.freq_masks + 2 * self.time_masks
+
+    def draw(self, rng):
+        """the n_draws uniforms of one utterance from `rng`, float64: (u_c, u_d), (u_f, u_f0)..., (u_t, u_t0)..."""
+        return rng.random_sample(self.n_draws)
+
+    def plan(self, draws, frames, F):
+        """K draws, the K frame counts (the `input_sizes` of the batch, behind the cut to max_frames) and the feature rows F -> SpecPlan,
+        int32 (K, 3 + 2 freq_masks + 2 time_masks): tau, c, w, (f0, f)..., (t0, t)..."""
+        frames, F = np.array(frames, dtype=np.int64).reshape(-1), int(F)
+        K, W, mF = len(frames), self.time_warp, self.freq_masks
+        draws = np.array(draws, dtype=np.float64).reshape(K, -1)
+        if draws.shape[1] != self.n_draws:
+            raise ValueError('SpecAugment.plan: %d uniforms per utterance, this policy takes %d' % (draws.shape[1], self.n_draws))
+        if self.freq_width > F:
+            raise ValueError('SpecAugment.plan: freq_width=%d is more than the %d feature rows' % (self.freq_width, F))
+        if (frames < 1).any():
+            raise ValueError('SpecAugment.plan: an utterance without frames')
+        if frames.max() > SPECAUG_MAX_FRAMES:
+            raise ValueError('SpecAugment.plan: a batch of %d frames is beyond the %d that the kernel covers (a row in 64 KB of LDS)'
+                             % (frames.max(), SPECAUG_MAX_FRAMES))
+        table = np.zeros((K, 3 + self.n_draws - 2), dtype=np.int64)
+        for k in range(K):
+            tau, u = int(frames[k]), draws[k]
+            table[k, 0] = tau
+            if W >= 1 and tau >= 2 * W + 1:
+                c = W + int(np.floor(u[0] * (tau - 2 * W)))
+                table[k, 1], table[k, 2] = c, c + int(np.floor(u[1] * (2 * W - 1))) - (W - 1)
+            for m in range(mF):
+                f = int(np.floor(u[2 + 2 * m] * (self.freq_width + 1)))
+                table[k, 3 + 2 * m], table[k, 4 + 2 * m] = int(np.floor(u[3 + 2 * m] * (F - f + 1))), f
+            cap = min(self.time_width, int(np.floor(self.time_ratio * tau)))
+            for m in range(self.time_masks):
+                t = int(np.floor(u[2 + 2 * mF + 2 * m] * (cap + 1)))
+                table[k, 3 + 2 * mF + 2 * m], table[k, 4 + 2 * mF + 2 * m] = int(np.floor(u[3 + 2 * mF + 2 * m] * (tau - t + 1))), t
+        return SpecPlan(table, mF, self.time_masks)
+
+
+class _SpecStage:
+    """The SpecAugment table of a `batch` call.  Host part: the checks of the table against the K final frame counts.  Device part: the
+    table in one pinned buffer, then mtl_spec_augment on the finished batch, in place."""
+
+    def __init__(self, spec, frames):
+        if isinstance(spec, tuple):
+            spec = SpecPlan(*spec)
+        mF, mT = getattr(spec, 'freq_masks', None), getattr(spec, 'time_masks', None)
+        if mF is None or mT is None:
+            raise ValueError('batch: spec= takes the table of SpecAugment.plan, or (table, freq_masks, time_masks)')
+        self.table, self.freq_masks, self.time_masks = np.ascontiguousarray(spec, dtype=np.int32).reshape(-1, 3 + 2 * mF + 2 * mT), mF, mT
+        if not (0 <= mF <= SPECAUG_MAX_MASKS and 0 <= mT <= SPECAUG_MAX_MASKS):
+            raise ValueError('batch: at most %d masks of either kind, the spec table has %d and %d' % (SPECAUG_MAX_MASKS, mF, mT))
+        if self.table.shape[0] != len(frames) or not np.array_equal(self.table[:, 0], frames):
+            raise ValueError('batch: the spec table was made for the frame counts %s, the batch has %s (SpecAugment.plan takes the final '
+                             'ones: behind rate conversion, tempo change and the cut to max_frames)'
+                             % (self.table[:, 0].tolist(), np.asarray(frames).tolist()))
+        if int(frames.max()) > SPECAUG_MAX_FRAMES:
+            raise ValueError('batch: a batch of %d frames is beyond the %d that mtl_spec_augment covers' % (frames.max(), SPECAUG_MAX_FRAMES))
+
+    def upload(self, staging, device):
+        self.d_table = staging.upload('spec', [self.table], 256, device)
+
+    def launch(self, lib, stream, inputs, K, F, tmax):
+        from . import _lib
+        _lib.check(lib.mtl_spec_augment(stream, inputs.data_ptr(), K, F, tmax, self.d_table.data_ptr(), self.freq_masks, self.time_masks),
+                   'mtl_spec_augment')
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # The pipeline, and the two feature types behind it
 # ------------------------------------------------------------------------------------------------------------------
 class BatchFrontEnd:
@@ -565,7 +697,7 @@ class BatchFrontEnd:
         self.stream = None                                     # batch()'s own stream, made at its first call
         self._staging = _Staging()                             # pinned staging of batch(), grown on demand
 
-    def batch(self, waves, max_frames=None, noise=None, augment=None, rates=None):
+    def batch(self, waves, max_frames=None, noise=None, augment=None, rates=None, spec=None):
         """K waveforms -> (inputs (K, 1, F, Tmax) fp32 on the device, input_sizes (K) int32 on the host): what `collate` builds from
         K `__call__` results cut to max_frames, in one device pass -- one pinned staging copy of the concatenated samples and of the
         offsets (two H2D copies) and the feature type's launch (framing, transform, logarithm, per-utterance statistics over the WHOLE
@@ -603,10 +735,20 @@ class BatchFrontEnd:
         (K int64, K float32) travel through pinned staging like the offsets; the call is mtl_wave_mix_coef, and the feature launch
         mixes (the feature types say how).
 
-        Each of the three left at None issues exactly the calls of the others.  The library calls of one `batch`, in order, all on the
+        A fourth optional stage runs BEHIND the feature launch, on the finished batch, on the same stream under the same event:
+
+        spec=the table of `SpecAugment.plan` (or (table, freq_masks, time_masks)), made for the K FINAL frame counts -- the input_sizes
+        that this call returns, behind rate conversion, tempo change and the cut to max_frames: SpecAugment (time warp, frequency masks,
+        time masks; `SpecAugment` for the definition) on the normalised (K, 1, F, Tmax) batch in place -- ONE launch, mtl_spec_augment.
+        The result is `batch(waves, ...)` with the same other arguments put through that definition; columns at and beyond an
+        utterance's own frame count stay the zeros they are.  The table (K int32 rows) travels through pinned staging like the other
+        plans.  No random draw is involved here.  A batch of more than 16384 frames is refused (ValueError).
+
+        Each of the four left at None issues exactly the calls of the others.  The library calls of one `batch`, in order, all on the
         front-end's stream: [mtl_resample], [mtl_tempo_search, mtl_tempo_render], [mtl_wave_mix_coef], then the feature launch --
         mtl_spect_batch, or mtl_spect_batch_noise behind a noise stage, for the spectrogram; [mtl_wave_mix behind a noise stage],
-        mtl_fbank_batch for the filterbank (tests/test_frontend_pipeline_gpu.py holds every combination to this)."""
+        mtl_fbank_batch for the filterbank (tests/test_frontend_pipeline_gpu.py holds every combination to this) -- and last
+        [mtl_spec_augment] (tests/test_specaug_gpu.py)."""
         from . import _lib
         if self.device.type != 'cuda':
             raise RuntimeError('the %s front-end runs on the MI355X only (no CPU fallback)' % self._NAME)
@@ -629,6 +771,7 @@ class BatchFrontEnd:
             stages.append(_NoiseStage(lengths, noise, self.device))
         frames = _cut(self._frame_counts(lengths), max_frames)
         K, tmax = len(frames), int(frames.max())
+        spec = None if spec is None else _SpecStage(spec, frames)
         ws_bytes = self._workspace_bytes(lib, lengths, K)
         if self.stream is None:
             self.stream = torch.cuda.Stream(self.device)
@@ -636,9 +779,13 @@ class BatchFrontEnd:
             inputs = torch.empty(K, 1, self.F, tmax, device=self.device)
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
             # 2. stage everything, upload it and launch, in order
+            if spec is not None:
+                spec.upload(self._staging, self.device)
             d_wav, d_off = _run_stages(lib, self.stream.cuda_stream, self._staging, self.device, stages, np.concatenate(arrs), offsets)
-            # 3. the feature launch, the event, the wait and the record
+            # 3. the feature launch, the stage behind it, the event, the wait and the record
             self._features_launch(lib, d_wav, d_off, K, inputs, tmax, ws, ws_bytes, stages[-1].mix if noise is not None else None)
+            if spec is not None:
+                spec.launch(lib, self.stream.cuda_stream, inputs, K, self.F, tmax)
             done = torch.cuda.Event()
             done.record(self.stream)
         done.synchronize()                                     # host wait on this stream's event only

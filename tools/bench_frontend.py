@@ -58,6 +58,18 @@ over the K waveforms rounded to 16-bit values:
 plus the HIP-event times of the two launches of mtl_fbank_batch and of mtl_spect_batch alone (operands already on the device).
 
     python tools/bench_frontend.py --logfbank --logfbank-out profiles/frontend_logfbank.json
+
+--specaug [--specaug-out PATH] runs the SpecAugment leg instead, same protocol, two paths that alternate, for the
+spectrogram and for the log-mel filterbank front-end:
+
+  (a) clean:     `batch(waves)`
+  (b) augmented: `batch(waves, spec=table)`, the default policy (W = 40, two frequency masks of up to 27 rows, two time masks of up to 40
+                 frames), seeded draws (an utterance whose draw gives w == c is not warped: `warped_utterances` counts the others)
+
+plus the HIP-event time of mtl_spec_augment alone on a finished batch and the bytes it reads and writes over that time (a warped row is
+read and written over [0, tau), a frequency-masked row written, any other row written over its time spans), against the HBM rate.
+
+    python tools/bench_frontend.py --specaug --specaug-out profiles/frontend_specaug.json
 """
 import argparse
 import json
@@ -94,6 +106,8 @@ def main():
     ap.add_argument('--resample-out', default=None)
     ap.add_argument('--logfbank', action='store_true')
     ap.add_argument('--logfbank-out', default=None)
+    ap.add_argument('--specaug', action='store_true')
+    ap.add_argument('--specaug-out', default=None)
     a = ap.parse_args()
     if a.reps < 20 or a.warmup < 3:
         ap.error('at least 20 timed calls after at least 3 warm-ups')
@@ -113,6 +127,8 @@ def main():
         return resample_leg(a, mtl_amd, _lib, fe, waves)
     if a.logfbank or a.logfbank_out:
         return logfbank_leg(a, mtl_amd, _lib, fe, waves, labels)
+    if a.specaug or a.specaug_out:
+        return specaug_leg(a, mtl_amd, _lib, fe, waves)
 
     def per_utterance():
         specs = [fe(y).cpu() for y in waves]
@@ -519,6 +535,115 @@ def resample_leg(a, mtl_amd, _lib, fe, waves16):
     print(json.dumps(res))
     if a.resample_out:
         with open(a.resample_out, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write('\n')
+
+
+HBM_ACHIEVABLE_TBPS = 6.3          # what a streaming copy reaches of the 8 TB/s (DESIGN.md section 21 quotes the same figure)
+
+
+def specaug_bytes(table, F, freq_masks, time_masks):
+    """the bytes that mtl_spec_augment moves for this table: per (utterance, row) 4 tau written under a frequency mask, else 8 tau (read and
+    written) when warped, else 4 per frame under a time mask"""
+    total = 0
+    for row in np.asarray(table):
+        tau, c, w = (int(v) for v in row[:3])
+        rows = np.zeros(F, dtype=bool)
+        for m in range(freq_masks):
+            rows[row[3 + 2 * m]:row[3 + 2 * m] + row[4 + 2 * m]] = True
+        cols = np.zeros(tau, dtype=bool)
+        for m in range(time_masks):
+            t0, t = row[3 + 2 * freq_masks + 2 * m], row[4 + 2 * freq_masks + 2 * m]
+            cols[t0:t0 + t] = True
+        total += int(rows.sum()) * 4 * tau + int((~rows).sum()) * (8 * tau if w != c else 4 * int(cols.sum()))
+    return total
+
+
+def specaug_leg(a, mtl_amd, _lib, fe, waves):
+    K, dev = len(waves), fe.device
+    sa = mtl_amd.SpecAugment()
+    fes = dict(spectrogram=fe, logfbank=mtl_amd.LogFBankFrontEnd(16000, 80, normalize=True))
+    rng = np.random.RandomState(23)
+    draws = [sa.draw(rng) for _ in range(K)]
+    tables = {}
+    for name, f in fes.items():
+        clean, sizes = f.batch(waves)
+        tables[name] = sa.plan(draws, sizes.numpy(), f.F)
+        got = f.batch(waves, spec=tables[name])[0]
+        torch.cuda.synchronize()
+        assert got.shape == clean.shape and not torch.equal(got, clean) and bool(torch.isfinite(got).all())
+        del clean, got
+
+    m = torch.randn(4096, 4096, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        m @ m
+    e0.record()
+    for _ in range(20):
+        m @ m
+    e1.record()
+    torch.cuda.synchronize()
+    chain = max(int(round(a.queued_ms / (e0.elapsed_time(e1) / 20))), 1)
+
+    def timed(fn, busy):
+        torch.cuda.synchronize()
+        if busy:
+            for _ in range(chain):
+                m @ m
+        t0 = time.perf_counter()
+        x = fn()
+        dt = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        del x
+        return dt
+
+    paths = []
+    for name, f in fes.items():
+        paths.append((name + '_clean', lambda f=f: f.batch(waves)[0]))
+        paths.append((name + '_specaug', lambda f=f, t=tables[name]: f.batch(waves, spec=t)[0]))
+    times = {(name, busy): [] for name, _ in paths for busy in (False, True)}
+    for rep in range(a.warmup + a.reps):
+        for busy in (False, True):
+            for name, fn in paths:
+                dt = timed(fn, busy)
+                if rep >= a.warmup:
+                    times[(name, busy)].append(dt)
+
+    # device time of the launch alone, on a finished batch (in place: every repetition moves the same bytes)
+    lib = _lib.lib()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    launch = {}
+    for name, f in fes.items():
+        x = f.batch(waves)[0]
+        t = tables[name]
+        d_t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+        us = []
+        for rep in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(lib.mtl_spec_augment(st, x.data_ptr(), K, f.F, x.size(3), d_t.data_ptr(), t.freq_masks, t.time_masks), 'mtl_spec_augment')
+            e1.record()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                us.append(1e3 * e0.elapsed_time(e1))
+        moved = specaug_bytes(t, f.F, t.freq_masks, t.time_masks)
+        tbps = moved / (statistics.median(us) * 1e-6) / 1e12
+        launch[name] = dict(launch_us_median=statistics.median(us), launch_us_min=min(us), launch_bytes=moved, batch_bytes=4 * x.numel(),
+                            launch_tb_per_s=tbps, launch_share_of_hbm_rate=tbps / HBM_TBPS, launch_share_of_achievable_hbm_rate=tbps / HBM_ACHIEVABLE_TBPS, rows=f.F,
+                            frames=int(x.size(3)), warped_utterances=int((t[:, 1] != t[:, 2]).sum()))
+
+    key = lambda n, b: '%s_%s' % (n, 'busy' if b else 'idle')
+    res = dict(device=torch.cuda.get_device_name(0), utterances=K, samples_per_utterance=len(waves[0]), reps=a.reps, warmup=a.warmup,
+               queued_ms=a.queued_ms, queued_products=chain, policy=dict(time_warp=sa.time_warp, freq_masks=sa.freq_masks,
+                                                                         freq_width=sa.freq_width, time_masks=sa.time_masks,
+                                                                         time_width=sa.time_width, time_ratio=sa.time_ratio),
+               utt_per_s={key(n, b): K / statistics.median(v) for (n, b), v in times.items()},
+               call_ms_median={key(n, b): 1e3 * statistics.median(v) for (n, b), v in times.items()},
+               call_ms_min_max={key(n, b): [1e3 * min(v), 1e3 * max(v)] for (n, b), v in times.items()},
+               hbm_tb_per_s=HBM_TBPS, hbm_achievable_tb_per_s=HBM_ACHIEVABLE_TBPS, launch=launch)
+    print(json.dumps(res))
+    if a.specaug_out:
+        with open(a.specaug_out, 'w') as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write('\n')
 
